@@ -11,31 +11,41 @@ samples resident in HBM (131 071 spectra per channel per step).  A step is one p
 path over one such batch; the steps rotate over --batches distinct batches (default 3, different
 seeds, separate output buffers) so that every step reads its samples from HBM — with a single
 268 MB batch re-processed every step, part of it can survive in the 256 MB Infinity Cache between
-steps (reported separately as `same_batch`).  Before anything is timed the GPU is brought to its
+steps (with --full, reported separately as `same_batch`).  Before anything is timed the GPU is brought to its
 sustained clocks with --prewarm-ms of the same launches: straight after start-up a 55-launch run
 sits inside the clock ramp and reads 17 % slow.  With N GPUs every rank owns its own channel(s)
 (weak scaling, no data-path collective); `value` is the whole-job spectra/s: total spectra of all
 ranks / max-over-ranks time.
 
-One JSON line is printed by rank 0; besides the contract fields it carries
+A plain run sets up, pre-warms, runs the W warm-up steps and the K timed steps, writes the last timed
+step's outputs when --dump-outputs DIR is given, and prints the line.  One JSON line is printed by
+rank 0; besides the contract fields it carries
   roofline      HBM roofline of the dominant kernel (stft_kernel): algorithmic bytes per launch
                 (4*hop + 4*(N/2+1) = 4100 B per spectrum) / average launch duration measured with
-                HIP events on the launch stream, against the 8 TB/s peak
-  parity        the colour image of the timed batch against the oracle on a sample of frames:
-                pixels checked / differing, split into "the epilogue given its float32 PSD"
-                (exact) and "float32 PSD moved a bin across an index edge"
-  cpu_baseline  the oracle (numpy restatement of the reference path, 1 core and all cores) timed on
-                a bounded sample of the same input on this box's host
-  legs          the other BASELINE configurations on this GPU's shard, each with its own roofline:
-                configs[2] 1/3-octave bank 8 ch (exact IIR time-parallel, exact IIR sequential
-                = the bit-exact mode, FIR overlap-add bank), configs[3] 16384-point STFT 32 ch,
-                configs[4] GCC-PHAT 100 window pairs + 1/24-octave bank 8 ch
+                HIP events on the launch stream (the timed steps), against the 8 TB/s peak
   ranks_seen    the ranks an all-gather over the job's process group returned (RCCL on GPUs); the job exits non-zero
                 unless they are exactly 0..N-1
   per_rank      every rank's own wall time per step (min / max / all): what the max-over-ranks hides
   slab_gather   with --gather-slabs: the optional all-gather of the output slabs, issued asynchronously
                 behind each step and overlapped with the next one; `value` then includes its cost
-Exit status: 0, or 3 when a parity gate of the timed batch fails (the JSON line is printed either way).
+With --full the run then measures and checks everything else, and the line also carries
+  roofline.kernel_ms_repeats, same_batch, packed_rows, psd_output
+                the timed launches twice more, the same batch every step, packed rows, the PSD kind
+  digest        per-channel mean of the timed batch's output, all-gathered
+  parity        the colour image of the timed batch against the oracle on a sample of frames:
+                pixels checked / differing, split into "the epilogue given its float32 PSD"
+                (exact) and "float32 PSD moved a bin across an index edge"
+  cpu_baseline  the oracle (numpy restatement of the reference path, 1 core and all cores) timed on
+                a bounded sample of the same input on this box's host
+  legs          the other BASELINE configurations on this GPU's shard, each with its own roofline (not with --no-legs):
+                configs[2] 1/3-octave bank 8 ch (exact IIR time-parallel, exact IIR sequential
+                = the bit-exact mode, FIR overlap-add bank), configs[3] 16384-point STFT 32 ch,
+                configs[4] GCC-PHAT 100 window pairs + 1/24-octave bank 8 ch
+--dump-outputs DIR writes the arrays the timed path hands its caller after the last timed step (split layout:
+<kind>_rows [ch][F][N/2] and <kind>_nyquist [ch][F]; packed: <kind> [ch][F][N/2+1]) as DIR/<name>.npy, colour pixels as
+float64, at most 48 MB in all (a fixed, seeded sample of frames, whose indices are frame_index.npy).  The inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
+Exit status: 0, or 3 when a parity gate of --full fails (the JSON line is printed either way).
 """
 from __future__ import annotations
 
@@ -279,6 +289,28 @@ def image_parity_report(eng, x, image, n_fft, hop, weight, lut, frames=4096):
                    "own float32 PSD (exact outside 1e-6 of an index edge); pixels_mismatched: against the float64 reference "
                    "image, i.e. bins the float32 PSD error (psd_rel_max of the frame maximum) carried across an edge")
     return rep
+
+
+DUMP_BUDGET_BYTES = 48 << 20      # --dump-outputs: at most this much float data in all (the frame index included)
+DUMP_SEED = 2024
+
+
+def dump_outputs(out_dir: Path, arrays: dict, frames: int, prefix: str = "") -> None:
+    """--dump-outputs: the output arrays of one step, [channels][frames]... each, written as out_dir/<prefix><name>.npy.  Colour pixels
+    (32-bit ARGB words) become float64, which holds them exactly; float outputs keep float32.  When every frame does not fit the
+    budget, the same fixed, seeded sample of frames is taken from every array, and its indices are written as <prefix>frame_index.npy
+    (float64) either way."""
+    import torch
+    per_frame = sum(a[:, :1].numel() * (4 if a.dtype == torch.float32 else 8) for a in arrays.values()) + 8
+    n = min(frames, max(1, DUMP_BUDGET_BYTES // per_frame))
+    idx = np.arange(frames) if n == frames else np.sort(np.random.default_rng(DUMP_SEED).choice(frames, n, replace=False))
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / f"{prefix}frame_index.npy", idx.astype(np.float64))
+    sel = torch.from_numpy(idx).to(next(iter(arrays.values())).device)
+    for name, a in arrays.items():
+        v = a.index_select(1, sel).cpu().numpy()
+        v = v.view(np.uint32).astype(np.float64) if v.dtype == np.int32 else v.astype(np.float32)
+        np.save(out_dir / f"{prefix}{name}.npy", v)
 
 
 def timed(fn, steps, dev, distributed, torch):
@@ -569,14 +601,21 @@ def main():
     ap.add_argument("--batches", type=int, default=3, help="distinct input batches the steps rotate over (1 = same batch every step)")
     ap.add_argument("--prewarm-ms", type=float, default=300.0, help="untimed launches before the warm-up steps (GPU clock ramp)")
     ap.add_argument("--prewarm-batch", type=int, default=4, help="launches queued between two synchronisations of the pre-warm")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU work for cpu_baseline (0 = skip)")
-    ap.add_argument("--no-legs", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="with --full: seconds of CPU work for cpu_baseline (0 = skip)")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: no other BASELINE legs (profiling runs)")
     ap.add_argument("--gather-slabs", action="store_true", help="all-gather every step's output slab over the job's process group, "
                     "asynchronously behind the step and overlapped with the next one (SURVEY.md §8e; optional: nobody needs "
                     "every channel's slab on every GPU by default)")
     ap.add_argument("--full-json", default="", help="also write the uncompacted record (prose notes, full-precision floats) to this file")
     ap.add_argument("--stub-engine", action="store_true", help="tests only: CPU stand-in engine over gloo, see StubEngine")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: kernel-time repeats, "
+                    "same-batch / packed-row / PSD-output timings, the output digest, the parity report of the timed batch, the other "
+                    "BASELINE legs (unless --no-legs) and the CPU baseline (--cpu-budget)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step computed "
+                    "as DIR/<name>.npy (float32 / float64; a fixed, seeded sample of frames when the whole output exceeds the budget)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_under_torchrun(args.gpus)        # plain `python bench.py --gpus N`: becomes the contract's launch line (does not return)
@@ -694,14 +733,23 @@ def main():
     for k in range(args.warmup):
         step(k)
     # One HIP event pair brackets the K launches on the launch stream (torch's current stream, which the C ABI launches
-    # on): average launch duration = elapsed / K.  Repeated three times for the run-to-run spread; `value` is the FIRST.
+    # on): average launch duration = elapsed / K.  With --full repeated three times for the run-to-run spread; `value` is the FIRST.
     wall, kernel_ms = timed(step, args.steps, dev, distributed, torch)
     if gather is not None:
         gather.wait_all()
     elapsed = distributed.max_over_ranks(wall, dev)
     per_rank_wall = distributed.gather_scalars(wall, dev)
     kernel_ms_max = distributed.max_over_ranks(kernel_ms, dev)
-    repeats = [kernel_ms_max] + [distributed.max_over_ranks(timed(step, args.steps, dev, distributed, torch)[1], dev) for _ in range(2)]
+    if args.dump_outputs:
+        b_last = (args.steps - 1) % nbatch               # the buffers of the last timed step (nothing has written them since)
+        if split:
+            arrays = {f"{args.kind}_rows": rows[b_last].view(vdt[0]), f"{args.kind}_nyquist": nyqs[b_last].view(vdt[0])}
+        else:
+            arrays = {args.kind: outs[b_last].view(vdt[0])}
+        dump_outputs(Path(args.dump_outputs), arrays, F, "" if world == 1 else f"rank{rank}_")
+    repeats = None
+    if args.full:
+        repeats = [kernel_ms_max] + [distributed.max_over_ranks(timed(step, args.steps, dev, distributed, torch)[1], dev) for _ in range(2)]
     slab_check = None
     if gather is not None:
         # every rank's slab arrived: the receive buffer of batch 0 against what each rank holds (first pixel / PSD value of
@@ -712,11 +760,11 @@ def main():
         gathered_bytes = gather.bytes_per_gather
         gather = None                              # the remaining measurements run without it
     same_batch_ms = None
-    if nbatch > 1:
+    if args.full and nbatch > 1:
         same_batch_ms = distributed.max_over_ranks(timed(lambda k: step(k, False), args.steps, dev, distributed, torch)[1], dev)
     # the same launches into packed rows [F][N/2+1] (frt_stft_run, the layout the drop-in classes hand on): both layouts in one line
     packed_ms = None
-    if split and not stub:
+    if args.full and split and not stub:
         packed = [torch.empty((len(my_channels), F, n_fft // 2 + 1), dtype=odt, device=dev) for _ in range(nbatch)]
         pstep = lambda k: eng.run(kind, xs[k % nbatch], packed[k % nbatch])       # noqa: E731
         for k in range(args.warmup):
@@ -725,7 +773,7 @@ def main():
         del packed
     # the same transform with its plain PSD output (no dB / weighting / colour epilogue), for reference
     psd_ms = None
-    if kind == 3 and not stub:
+    if args.full and kind == 3 and not stub:
         kind, vdt[0] = 0, torch.float32
         for k in range(args.warmup):
             step(k)
@@ -733,26 +781,26 @@ def main():
         kind, vdt[0] = 3, odt
         for b in range(nbatch):
             step(b)                               # the images back in place (digest, parity)
-    if split:                                     # the timed batch's image in the packed shape the checks below are written for
-        out = torch.cat([rows[0], nyqs[0][..., None]], dim=2)
-    else:
-        out = outs[0]
 
-    # post-batch summary gather (outside the timed region): per-channel mean pixel/PSD digest
-    digest = out.to(torch.float64).mean(dim=(1, 2)).reshape(-1, 1)
-    digest_all = distributed.gather_channel_summaries(digest, n_channels)
-
-    parity = None
-    if rank == 0 and kind == 3 and not stub:
-        parity = image_parity_report(eng, xs[0], out, n_fft, hop, consts["weight"], consts["lut"])
-        parity["layout"] = "split rows + Nyquist plane of the timed launches, reassembled" if split else "packed"
-
+    digest_all, parity = None, None
+    if args.full:
+        if split:                                 # the timed batch's image in the packed shape the checks below are written for
+            out = torch.cat([rows[0], nyqs[0][..., None]], dim=2)
+        else:
+            out = outs[0]
+        # post-batch summary gather (outside the timed region): per-channel mean pixel/PSD digest
+        digest = out.to(torch.float64).mean(dim=(1, 2)).reshape(-1, 1)
+        digest_all = distributed.gather_channel_summaries(digest, n_channels)
+        if rank == 0 and kind == 3 and not stub:
+            parity = image_parity_report(eng, xs[0], out, n_fft, hop, consts["weight"], consts["lut"])
+            parity["layout"] = "split rows + Nyquist plane of the timed launches, reassembled" if split else "packed"
+        del out
 
     exit_code = 0
     legs = {}
-    if not stub and not args.no_legs and n_fft == 1024:
+    if args.full and not stub and not args.no_legs and n_fft == 1024:
         prepared.clear()                          # (the prepared launches hold their buffers)
-        del xs, outs, out
+        del xs, outs
         if split:
             del slabs, rows, nyqs
         torch.cuda.empty_cache()
@@ -811,7 +859,7 @@ def main():
                          "traffic_note": "HBM bytes per launch from the rocprofv3 PMC passes of this command (tools/gpu_session.sh -> "
                                          "profiles/pmc_traffic.json), quoted only when that file was measured on these kernel sources",
                          "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "kernel_ms": kernel_ms_max, "kernel_ms_repeats": repeats,
+                         "kernel_ms": kernel_ms_max,
                          # what the wall clock of the K timed steps holds beside the K launches' own time: the first launch's way to
                          # the device and the wake-up behind the last one (profiles/r06_host_fixed.txt: ~20 us per timed region,
                          # spinning on the completion signal instead of sleeping changes nothing); `value` stays on the wall clock
@@ -820,8 +868,11 @@ def main():
             "per_rank": {"ms_per_step_min": min(per_rank_wall) / args.steps * 1e3, "ms_per_step_max": max(per_rank_wall) / args.steps * 1e3,
                          "ms_per_step": [w / args.steps * 1e3 for w in per_rank_wall],
                          "note": "every rank's own wall time of the K timed steps between the two barriers; value uses the maximum"},
-            "digest": float(digest_all.sum().item()),
         }
+        if repeats is not None:
+            result["roofline"]["kernel_ms_repeats"] = repeats
+        if digest_all is not None:
+            result["digest"] = float(digest_all.sum().item())
         if slab_check is not None:
             result["slab_gather"] = {"enabled": True, "bytes_per_step_per_rank": gathered_bytes, "slabs_verified": slab_check,
                                      "note": "all_gather_into_tensor of the step's output slab, async behind the step, overlapped with "
@@ -842,7 +893,7 @@ def main():
         if legs:
             result["legs"] = legs
             result["octave_bands"] = legs.get("configs2_bank_iir_time_parallel")      # the metric's second half, as in round 1
-        if args.cpu_budget > 0:
+        if args.full and args.cpu_budget > 0:
             # rank 0 only, whatever the world size (after the timed region and after the process group is gone)
             base = cpu_baseline(host_x[0], n_fft, hop, consts["weight"], consts["lut"], args.cpu_budget, with_legs=bool(legs) or stub)
             side = base.pop("_side")

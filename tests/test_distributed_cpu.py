@@ -68,7 +68,7 @@ def test_two_rank_gloo_roundtrip():
 def test_bench_rank_logic_two_ranks_gloo():
     """bench.py end to end with WORLD_SIZE = 2 over gloo and its CPU stand-in engine (--stub-engine): channel sharding,
     table broadcast from rank 0, barrier-bracketed timing with max over ranks, digest all-gather, ranks_seen — the
-    contract's launch line, one JSON line from rank 0."""
+    contract's launch line, one JSON line from rank 0 (--full: the digest and the CPU baseline)."""
     import json
     import subprocess
     import sys
@@ -76,7 +76,7 @@ def test_bench_rank_logic_two_ranks_gloo():
     root = Path(__file__).resolve().parents[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(root / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--stub-engine", "--log2-samples", "14", "--batches", "2", "--cpu-budget", "1"]
+           "--stub-engine", "--log2-samples", "14", "--batches", "2", "--full", "--cpu-budget", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(root))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -195,6 +195,38 @@ def test_bench_stub_single_process():
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert rec["n_gpus"] == 1 and rec["ranks_seen"] == [0] and rec["roofline"]["traffic"] is None
+
+
+def test_bench_stub_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times the steps and prints the headline only; --dump-outputs writes the last timed step's rows and
+    Nyquist plane (float64 pixels) with their frame index, the same files for the same arguments."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    recs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--stub-engine", "--log2-samples", "14", "--steps", "4", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=300, cwd=str(root))
+        assert r.returncode == 0, r.stderr[-2000:]
+        recs.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0]))
+    rec = recs[0]
+    F = (2 ** 14 - 1024) // 512 + 1
+    assert rec["steps"] == 4 and abs(rec["value"] - F * 4 / (rec["ms_per_step"] * 4e-3)) <= 1e-6 * rec["value"]
+    for key in ("cpu_baseline", "parity", "legs", "digest", "same_batch", "packed_rows", "psd_output"):
+        assert key not in rec, key
+    assert "kernel_ms_repeats" not in rec["roofline"]
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["frame_index.npy", "image_nyquist.npy", "image_rows.npy"]
+    rows, nyq = np.load(tmp_path / "a" / "image_rows.npy"), np.load(tmp_path / "a" / "image_nyquist.npy")
+    assert rows.dtype == nyq.dtype == np.float64 and rows.shape == (1, F, 512) and nyq.shape == (1, F)
+    assert np.array_equal(np.load(tmp_path / "a" / "frame_index.npy"), np.arange(F, dtype=np.float64))
+    # the stub writes 1000 x the channel's first sample of the batch it ran; the last timed step (k = 3) ran batch 3 % 3 = 0
+    want = float(np.int32(1000 * (0.25 * np.random.default_rng(42).standard_normal(2 ** 14, dtype=np.float32))[0]).view(np.uint32))
+    assert np.all(rows == want) and np.all(nyq == want)
+    for name in names:
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)), name
 
 
 def _forced_solo_worker(port, q):

@@ -76,7 +76,7 @@ def test_bench_under_torchrun_on_rccl_with_one_rank():
     env = dict(os.environ, FRT_DIST_FORCE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29673", str(ROOT / "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--no-legs",
-           "--cpu-budget", "0", "--log2-samples", "22", "--gather-slabs"]
+           "--full", "--cpu-budget", "0", "--log2-samples", "22", "--gather-slabs"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=380, cwd=str(ROOT))
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -41,7 +41,7 @@ def main():
            "hbm_bytes_per_launch": read_b + write_b, "read_bytes": read_b, "write_bytes": write_b, "raw": raw,
            "check": {"TCC_EA0_RDREQ*128B": raw.get("TCC_EA0_RDREQ_sum", 0.0) * 128.0, "TCC_EA0_WRREQ*64B": raw.get("TCC_EA0_WRREQ_sum", 0.0) * 64.0},
            "dispatches": {k: len(v) for k, v in acc.items()},
-           "method": "rocprofv3 --kernel-trace --pmc <one counter set per pass> -- python bench.py --steps 5 --warmup 2 --cpu-budget 0 "
+           "method": "rocprofv3 --kernel-trace --pmc <one counter set per pass> -- python bench.py --full --steps 5 --warmup 2 --cpu-budget 0 "
                      "--prewarm-ms 0 --no-legs; mean over the kernel's dispatches; FETCH_SIZE doubled per MI355X_MICROARCH.md",
            "algorithmic_bytes_per_launch": 131071 * 4100,
            "kernel_sources_note": "digest of the code of stft_wave.h + fft_core.h + stft_launch of stft.hip (comments and blank lines removed) at the "
