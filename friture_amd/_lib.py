@@ -105,6 +105,22 @@ SIGNATURES = {
     "frt_delay_window": (c_int, [c_void_p, c_int64, c_int, POINTER(c_void_p), POINTER(c_void_p)]),
     "frt_delay_window_std": (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_double)]),
     "frt_delay_demean": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "frt_levels_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int64, POINTER(c_double), c_int, c_double, c_double,
+                                  POINTER(c_double), POINTER(c_double), c_double]),
+    "frt_levels_destroy": (None, [c_void_p]),
+    "frt_levels_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_levels_reset": (c_int, [c_void_p]),
+    "frt_levels_set_ndec": (c_int, [c_void_p, c_int]),
+    "frt_levels_state_length": (c_int64, [c_void_p]),
+    "frt_levels_get_state": (c_int, [c_void_p, POINTER(c_double)]),
+    "frt_levels_set_state": (c_int, [c_void_p, POINTER(c_double)]),
+    "frt_levels_blocks_for": (c_int64, [c_void_p, c_int64]),
+    "frt_levels_pending": (c_int64, [c_void_p]),
+    "frt_levels_run": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
+    "frt_levels_push": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
+    "frt_levels_subsample_length": (c_int64, [c_void_p, c_int64]),
+    "frt_levels_subsample": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, POINTER(c_int64)]),
+    "frt_levels_history": (c_int, [c_void_p, c_int64, c_void_p]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

@@ -369,6 +369,60 @@ int64_t frt_pitch_frames_for(const frt_pitch* h, int64_t T);
 int frt_pitch_track(frt_pitch* h, const double* x, int64_t T, int64_t x_stride, double* f0_out, double* raw_out,
                     int64_t* n_frames_out);
 
+/* ---- L1: level meters and long-time levels (Levels_Widget, LongLevelWidget) -----------------------------
+ * Per channel and per chunk (friture/levels.py:85-124, iec.py, ballistic_peak.py:21-66,
+ * signal/exp_smoothing.py:40-56): value_max = max|y| (chunks of length > 0); old_max = value_max if
+ * value_max > old_max (1 - alpha2), else old_max *= (1 - alpha2); rms = alpha (kernel tail . y^2) +
+ * rms (1 - alpha)^len (an empty chunk keeps rms); level_rms = 10 log10(rms), level_max = 20 log10(old_max);
+ * peak_iec = BallisticPeak(dB_to_IEC(max(level_max, level_rms))), the hold-then-decay machine whose decay
+ * factor squares itself on every decay step.  Per complete block of 2^Ndec samples (friture/longlevels.py:
+ * 31-91,138-171,195-209; a block is the 2^Ndec samples ending where the previous one ended plus 2^Ndec, i.e. the
+ * widget's data_indexed(old_index, 2^Ndec): one block behind the stream, zeros before its start): y^2 -> Ndec x (FIR gauss11 with a = [1, 0, ...], then [::2]) -> FIR gauss41 with
+ * carried state -> 10 log10(max(level, 1e-150)) -> a history ring of history_len entries.
+ * kernel[nk], alpha, alpha2, gauss11[11], gauss41[41] and peak_decay_rate are the reference's own host values
+ * (levels.py:57-74, longlevels.py:49-51,61,220-221, ballistic_peak.py:22); the handle carries every state
+ * across calls, per channel.  Ndec 1 .. 13. */
+typedef struct frt_levels frt_levels;
+#define FRT_LEVELS_METER_FIELDS 6  /* rms, old_max, level_rms, level_max, peak_iec, branch                  */
+#define FRT_LEVELS_FOLLOW 0        /* ballistic_peak.py:43-47  the input is above the peak                  */
+#define FRT_LEVELS_HOLD 1          /* ballistic_peak.py:48-51  hold                                         */
+#define FRT_LEVELS_DECAY 2         /* ballistic_peak.py:52-62  decay; the factor squares itself             */
+#define FRT_LEVELS_DECAY_FLOOR 3   /* ballistic_peak.py:55-58  decay below the input: follow it, reset hold */
+int frt_levels_create(frt_levels** h, int channels, int ndec, int64_t history_len, const double* kernel, int nk, double alpha,
+                      double alpha2, const double* gauss11, const double* gauss41, double peak_decay_rate);
+void frt_levels_destroy(frt_levels* h);
+int frt_levels_set_stream(frt_levels* h, void* hip_stream);
+/* every state to its initial value (levels.py:66-69, ballistic_peak.py:27-29, longlevels.py:225-229), ring zeroed */
+int frt_levels_reset(frt_levels* h);
+/* LongLevelWidget.setresptime (longlevels.py:212-229): new Ndec, zero subsampler and FIR state; the samples not
+ * yet consumed, the meters and the ring are kept */
+int frt_levels_set_ndec(frt_levels* h, int ndec);
+/* the carried state as doubles: [pending count, Ndec, channels x (meters, stage inputs, FIR inputs, pending)] */
+int64_t frt_levels_state_length(const frt_levels* h);
+int frt_levels_get_state(frt_levels* h, double* state);
+int frt_levels_set_state(frt_levels* h, const double* state);
+/* blocks a call with n more samples per channel produces; samples received and not yet consumed (< 2^Ndec) */
+int64_t frt_levels_blocks_for(const frt_levels* h, int64_t n);
+int64_t frt_levels_pending(const frt_levels* h);
+/* Batch form.  x: [channels][ld] float32 (dtype 0) or float64 (dtype 1), host or device; cut into chunks of
+ * `chunk` samples (a short last chunk is a short chunk).  meters_out (or NULL: no meters):
+ * [channels][ceil(n / chunk)][FRT_LEVELS_METER_FIELDS]; long_out (or NULL: no long levels, nothing carried):
+ * [channels][nblocks][2] = {level, level dB}.  Host or device outputs. */
+int frt_levels_run(frt_levels* h, const void* x, int dtype, int64_t n, int64_t ld, int64_t chunk, double* meters_out,
+                   double* long_out, int64_t* nblocks);
+/* Interactive form: one handle_new_data of channels [0, nch) — the whole push is one chunk, n = 0 is the
+ * reference's empty chunk.  x_host: [nch][n] float64; meters_out [nch][FRT_LEVELS_METER_FIELDS] or NULL;
+ * long_out [nch][nblocks][2] or NULL (needs nch = channels).  One upload, the launches, one download. */
+int frt_levels_push(frt_levels* h, const double* x_host, int nch, int64_t n, double* meters_out, double* long_out,
+                    int64_t* nblocks);
+/* Subsampler.push (longlevels.py:54-91): x through the Ndec stages as given (no squaring), [::2] keeping index 0
+ * of THIS call at every stage; out [channels][nout] (host or device).  Uses the stage state only. */
+int64_t frt_levels_subsample_length(const frt_levels* h, int64_t n);
+int frt_levels_subsample(frt_levels* h, const void* x, int dtype, int64_t n, int64_t ld, double* out, int64_t* nout);
+/* the last `count` <= history_len ring entries per channel, oldest first, 0 where nothing was pushed yet:
+ * out [channels][count] (host or device) */
+int frt_levels_history(frt_levels* h, int64_t count, double* out);
+
 #ifdef __cplusplus
 }
 #endif
