@@ -121,6 +121,9 @@ SIGNATURES = {
     "frt_levels_subsample_length": (c_int64, [c_void_p, c_int64]),
     "frt_levels_subsample": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, POINTER(c_int64)]),
     "frt_levels_history": (c_int, [c_void_p, c_int64, c_void_p]),
+    "frt_scope_trace_length": (c_int64, [c_int64, c_int]),
+    "frt_scope_run": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64, POINTER(c_int64), c_int64, c_int64, c_int,
+                              c_void_p, c_void_p, c_int]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

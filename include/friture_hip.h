@@ -423,6 +423,29 @@ int frt_levels_subsample(frt_levels* h, const void* x, int dtype, int64_t n, int
  * out [channels][count] (host or device) */
 int frt_levels_history(frt_levels* h, int64_t count, double* out);
 
+/* ---- S1: oscilloscope (Scope_Widget) ----------------------------------------------------------------------------------
+ * Per refresh k of stream s, the stream seen up to e = ends[k] (samples before index 0 are zeros, as in a fresh ring), width w
+ * (int(timerange * 1e-3 * SAMPLING_RATE), host arithmetic), h = w / 2 (friture/scope.py:78-135):
+ *   trigger mode (scrolling = 0, timerange <= 500 ms): the region is the w samples x[r0, r0 + w) of row 0, r0 = e - 2w + h;
+ *     level = (max(region) * 2.) / 3. in float64 (a NaN in the region: no trigger); the trigger is the first i with
+ *     region[i] < level && region[i + 1] >= level; the trace is x[:, e - 2w + i, e - 2w + i + 2h) of every row.
+ *   scrolling mode (scrolling = 1, timerange > 500 ms): the trace is x[:, e - w, e), always.
+ * Float32 input is compared in float64 (a float32 sample widens exactly; the level is never rounded to float32). */
+#define FRT_SCOPE_NO_TRIGGER (-9223372036854775807LL - 1) /* start_out of a refresh without a crossing             */
+#define FRT_SCOPE_TRACE_RAW 1                              /* trace_kind bit: the samples y                          */
+#define FRT_SCOPE_TRACE_SCALED 2                           /* trace_kind bit: scaled_y = 1. - (y + 1) / 2. (scope.py:129) */
+/* samples per trace row: 2 (width / 2) in trigger mode, width in scrolling mode */
+int64_t frt_scope_trace_length(int64_t width, int scrolling);
+/* x: streams x rows x n samples, x[s * ld_stream + r * ld_row + t], float32 (dtype 0) or float64 (dtype 1), host or device
+ * (a host input is staged as the whole span it covers).  ends: [n_refresh] HOST int64, sorted, each in [0, n].  Only row 0
+ * of each stream triggers; the other rows are cut at the same place.
+ * start_out: [streams][n_refresh] absolute index of the trace's first sample (may be negative), FRT_SCOPE_NO_TRIGGER when no
+ * crossing was found.  trace_out (or NULL): for each bit set in trace_kind, raw first, a block of
+ * [streams][rows][n_refresh][frt_scope_trace_length] doubles; written only for the refreshes that triggered.  Host or device
+ * outputs; one synchronisation at the end.  width < 1: FRT_ERR_INVALID (the reference raises on an empty region). */
+int frt_scope_run(const void* x, int dtype, int streams, int rows, int64_t n, int64_t ld_row, int64_t ld_stream, const int64_t* ends,
+                  int64_t n_refresh, int64_t width, int scrolling, int64_t* start_out, double* trace_out, int trace_kind);
+
 #ifdef __cplusplus
 }
 #endif
