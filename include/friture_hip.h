@@ -446,6 +446,26 @@ int64_t frt_scope_trace_length(int64_t width, int scrolling);
 int frt_scope_run(const void* x, int dtype, int streams, int rows, int64_t n, int64_t ld_row, int64_t ld_stream, const int64_t* ends,
                   int64_t n_refresh, int64_t width, int scrolling, int64_t* start_out, double* trace_out, int trace_kind);
 
+/* ---- P1: spectrum / octave-spectrum plot curves with peak hold (SpectrumPlotWidget, HistPlot) ----------------------------
+ * Per refresh r of stream s, y the row of `bins` dB values (friture/spectrumPlotWidget.py:122-200, friture/histplot.py:77-130):
+ *   toScreen(v) = (v - cmin) / (cmax - cmin), or 0 + 0. * v when cmax == cmin (NaN for +-inf and NaN)
+ *   scaled_y = 1. - toScreen(y);  z = (y - cmin) / (|M - cmin| + 1e-3), M = max(y) with NaN propagating
+ *   peak hold on the old state (peak, int, decay): peak < y -> (y, 1, c); else int < 0.2 -> peak += decay, decay += c;
+ *     else int *= 0.975;  c = frt_curves_decay_step() = 20 log10(1 - 3e-6) 5000
+ *   scaled_peak = 1. - toScreen(peak);  z_peak = int
+ * All in float64; float32 input is widened first.  The caller swaps a reversed range and resets the state on a bin-count
+ * change (peak -500, int 0, decay c), as the widgets do. */
+double frt_curves_decay_step(void);
+/* y: y[s * ld_stream + r * ld_refresh + b], float32 (dtype 0) or float64 (dtype 1), host or device (a host input is staged as
+ * the whole span it covers).  state: [streams][3][bins] doubles (peak, int, decay), read, and written back when peaks != 0;
+ * peaks == 0 leaves it as it is (peak outputs then show it unchanged); may be NULL when peaks == 0 and no peak output is asked.
+ * scaled_y, z, scaled_peak, z_peak (each may be NULL): [streams][n_refresh][bins] doubles, or [streams][1][bins] with
+ * keep_last (the final refresh only; the state still walks every refresh).  Host or device inputs and outputs in any mix;
+ * one synchronisation at the end. */
+int frt_curves_run(const void* y, int dtype, int streams, int64_t n_refresh, int64_t bins, int64_t ld_refresh, int64_t ld_stream,
+                   double cmin, double cmax, double* state, int peaks, int keep_last, double* scaled_y, double* z,
+                   double* scaled_peak, double* z_peak);
+
 #ifdef __cplusplus
 }
 #endif
