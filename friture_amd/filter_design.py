@@ -7,7 +7,7 @@ them on demand (`design_all()`).  scipy's elliptic design changed between the ve
 used and current releases, so the re-derived numbers agree with upstream's to 1e-5 .. 4e-3 only;
 because every parity target is defined with upstream's numbers, the table the backend and the
 oracle load (friture_amd/data/octave_filters.npz) holds those numbers verbatim, extracted by
-tools/extract_reference_tables.py.  What is designed:
+oracle/golden_tables.py.  What is designed:
 
   * decimation low-pass: 12th-order elliptic, iirdesign(wp=0.48, ws=0.50, gpass=0.05, gstop=70)
   * band-passes of the top octave: ellip(2, 0.5 dB, 50 dB, [f_low, f_high]) for each of the

@@ -8,6 +8,7 @@ the reference lines it restates (paths relative to the reference checkout).
 Parity pin: upstream has no golden vectors for most of this path, so the
 oracle is pinned against the *reference itself*, executed unmodified in the build container
 through oracle/refshim.py; oracle/make_golden.py records those outputs in tests/golden/*.npz
+(and, with --check, compares what it records with the committed files)
 and tests/test_oracle_golden.py replays them wherever the tests run (including the GPU box,
 where the reference checkout does not exist).  The upstream property tests that do exist
 (friture/test/test_octave_filters.py:37-100 energy ±5 %, decimation ordering :63-72,
@@ -679,7 +680,7 @@ class TimeResampler:
 # but the reference's current estimate_pitch does not reproduce them (executed here through
 # oracle/refshim.py it returns nan for both: the candidates stop at max_freq = 1047 Hz and the
 # confidence gate rejects the 32-point frames).  The pin is therefore the reference code itself,
-# executed unmodified in the build container: oracle/make_golden_pitch.py -> tests/golden/pitch.npz.
+# executed unmodified in the build container: oracle/golden_pitch.py -> tests/golden/pitch.npz.
 
 SWIPE_HARMONICS = (1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 13, 17, 19, 23)     # friture/pitch_tracker.py:217
 

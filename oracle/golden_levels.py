@@ -1,85 +1,28 @@
-"""Record tests/golden/levels.npz from the reference's own Levels_Widget, LongLevelWidget and Subsampler.
+"""Record levels.npz from the reference's own Levels_Widget, LongLevelWidget and Subsampler.
 
-Runs only where the reference checkout is (oracle.refshim): stand-ins for the Qt and UI modules the widgets import, then the
-reference classes are driven chunk by chunk on the signals of tests/levels_helpers.py (regenerated from seeds there, never
-stored).  Recorded per meter step: rms, old_max, level_rms, level_max, peak_iec, the BallisticPeak branch (0 follow, 1 hold,
+Driven by oracle/make_golden.py (needs the reference checkout): the stand-ins of oracle/refshim.py plus the two settings
+dialogs, then the reference classes are driven chunk by chunk on the signals of tests/levels_helpers.py (regenerated from seeds
+there, never stored).  Recorded per meter step: rms, old_max, level_rms, level_max, peak_iec, the BallisticPeak branch (0 follow, 1 hold,
 2 decay, 3 decay below the input) and the margins of its comparisons; per long-level block: level and dB; the Subsampler's
 outputs; the curves handed to Curve.setData around setduration / setmin / setmax / setresptime; the coefficients.
-
-    python tools/make_golden_levels.py
 """
 from __future__ import annotations
 
 import hashlib
-import sys
 import types
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "tests"))
+from . import refshim
 
-import levels_helpers as H  # noqa: E402
-from oracle import refshim  # noqa: E402
-
-
-class _Signal:
-    def __init__(self, *a):
-        pass
-
-    def emit(self, *a):
-        pass
-
-    def connect(self, *a):
-        pass
-
-
-class _QObject:
-    def __init__(self, parent=None, *a, **k):
-        pass
-
-
-def _pyqt_property(*a, **k):
-    return lambda f: property(f)
-
-
-class _Recorder:
-    """Scope_Data / Curve / axis stand-in: accepts every call, records Curve.setData."""
-
-    def __init__(self, *a, **k):
-        self.calls = []
-        self.vertical_axis = self
-        self.horizontal_axis = self
-
-    def __getattr__(self, name):
-        return lambda *a, **k: None
-
-    def setData(self, x, y):
-        self.calls.append((np.array(x, copy=True), np.array(y, copy=True)))
+import levels_helpers as H  # noqa: E402  (tests/ is on sys.path once refshim is imported)
 
 
 def install_stubs():
     refshim.install()
-    qtcore = types.ModuleType("PyQt6.QtCore")
-    qtcore.QObject = _QObject
-    qtcore.pyqtSignal = _Signal
-    qtcore.pyqtProperty = _pyqt_property
-    sys.modules["PyQt6.QtCore"] = qtcore
-    sys.modules["PyQt6"].QtCore = qtcore
-
-    def module(name, **attrs):
-        m = types.ModuleType(name)
-        m.__dict__.update(attrs)
-        sys.modules[name] = m
-
-    module("friture.levels_settings", Levels_Settings_Dialog=_Recorder)
-    module("friture.longlevels_settings", LongLevels_Settings_Dialog=_Recorder, DEFAULT_LEVEL_MIN=-70, DEFAULT_LEVEL_MAX=-20,
-           DEFAULT_MAXTIME=600, DEFAULT_RESPONSE_TIME=20)
-    module("friture.scope_data", Scope_Data=_Recorder)
-    module("friture.curve", Curve=_Recorder)
-    module("friture.store", GetStore=lambda: None)
+    refshim.module("friture.levels_settings", Levels_Settings_Dialog=refshim.Any)
+    refshim.module("friture.longlevels_settings", LongLevels_Settings_Dialog=refshim.Any, DEFAULT_LEVEL_MIN=-70,
+                   DEFAULT_LEVEL_MAX=-20, DEFAULT_MAXTIME=600, DEFAULT_RESPONSE_TIME=20)
 
 
 class _BallisticProbe:
@@ -127,25 +70,12 @@ def run_levels(x, sizes=None):
     return np.array(rows[:x.shape[0]]), w
 
 
-class _AudioBuffer:
-    def __init__(self):
-        from friture.ringbuffer import RingBuffer
-        self.ringbuffer = RingBuffer()
-        self.lastDataTime = 0.
-
-    def push(self, x):
-        self.ringbuffer.push(x, 0.)
-
-    def data_indexed(self, start, length):
-        return self.ringbuffer.data_indexed(start, length)
-
-
 def long_widget(rt):
     from friture.longlevels import LongLevelWidget
     w = LongLevelWidget.__new__(LongLevelWidget)
     LongLevelWidget.__init__(w, None)
     w.setresptime(rt)
-    w.audiobuffer = _AudioBuffer()
+    w.audiobuffer = refshim.AudioBuffer()
     return w
 
 
@@ -177,7 +107,7 @@ def run_long_linear(x, rt):
     return np.array(lin), np.array(db)
 
 
-def main():
+def levels(out_dir):
     install_stubs()
     from friture.longlevels import LongLevelWidget, Subsampler, gauss
     from friture.levels import Levels_Widget
@@ -233,10 +163,4 @@ def main():
             k += 1
         else:
             getattr(w, step)(v)
-    out = ROOT / "tests" / "golden" / "levels.npz"
-    np.savez_compressed(out, **g)
-    print(f"{out}: {out.stat().st_size} bytes, {len(g)} arrays")
-
-
-if __name__ == "__main__":
-    main()
+    np.savez_compressed(out_dir / "levels.npz", **g)

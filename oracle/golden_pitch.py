@@ -1,42 +1,19 @@
-"""oracle/make_golden_pitch.py — record tests/golden/pitch.npz from the UNMODIFIED reference
-(friture/pitch_tracker.py executed through oracle/refshim.py with its Qt/UI imports stubbed) and
-check oracle/dsp.py's restatement against it.  Build container only (needs /root/reference).
-
-    python -m oracle.make_golden_pitch
+"""oracle/golden_pitch.py — record pitch.npz from the UNMODIFIED reference (friture/pitch_tracker.py
+executed through oracle/refshim.py with its Qt/UI imports stubbed) and check oracle/dsp.py's
+restatement against it.  Driven by oracle/make_golden.py (needs the reference checkout).
 """
-import sys
-import types
-from pathlib import Path
-
 import numpy as np
 
-from oracle import dsp, refshim
-
-GOLD = Path(__file__).resolve().parents[1] / "tests" / "golden"
+from . import dsp, refshim
 
 
 def import_reference_pitch_tracker():
     """friture.pitch_tracker pulls in the Qt widget stack at import time (pitch_tracker.py:31-55);
     only PitchTracker / calcCosineKernel / fastParabolicInterp are needed, so every UI module gets
-    a stand-in whose attributes are empty classes."""
+    a blank stand-in."""
     refshim.install()
-
-    class Blank:
-        def __init__(self, *a, **k):
-            pass
-
-    def stand_in(name):
-        m = types.ModuleType(name)
-        m.__getattr__ = lambda attr: type(attr, (Blank,), {})
-        sys.modules[name] = m
-        return m
-
-    for name in ("PyQt6.QtWidgets", "PyQt6.QtCore", "friture.audiobuffer", "friture.curve", "friture.pitch_tracker_data",
-                 "friture.store", "friture.plotting.coordinateTransform"):
-        stand_in(name)
-    import PyQt6
-    PyQt6.QtWidgets = sys.modules["PyQt6.QtWidgets"]
-    PyQt6.QtCore = sys.modules["PyQt6.QtCore"]
+    for name in ("friture.audiobuffer", "friture.pitch_tracker_data", "friture.plotting.coordinateTransform"):
+        refshim.blank(name)
     import friture.pitch_tracker as pt
     return pt
 
@@ -63,7 +40,7 @@ def signals(n_fft):
     }
 
 
-def main():
+def pitch(out_dir):
     pt = import_reference_pitch_tracker()
     from friture.ringbuffer import RingBuffer
     out = {}
@@ -111,9 +88,4 @@ def main():
     out["kat32_raw"] = np.array([tr.estimate_pitch(np.array([kat]))])
     print(f"oracle vs reference pitch tracker: worst relative difference {worst:.3e}")
     assert worst < 1e-12
-    np.savez_compressed(GOLD / "pitch.npz", **out)
-    print("wrote", GOLD / "pitch.npz", {k: v.shape for k, v in out.items() if not k.endswith("_x")})
-
-
-if __name__ == "__main__":
-    main()
+    np.savez_compressed(out_dir / "pitch.npz", **out)

@@ -1,4 +1,4 @@
-"""Shared by tools/make_golden_levels.py and the level tests: the fixture's input signals (regenerated from seeds, never
+"""Shared by oracle/golden_levels.py and the level tests: the fixture's input signals (regenerated from seeds, never
 stored) and a numpy restatement of the long-level path as raw-input tap sums — the form the kernels compute
 (friture_amd/csrc/levels.hip): y[n] = ((x[n-10] b10 + x[n-9] b9) + ...) + x[n] b0, elementwise IEEE operations."""
 from __future__ import annotations

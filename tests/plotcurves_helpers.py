@@ -1,4 +1,4 @@
-"""Test infrastructure for the spectrum / octave-spectrum plot curves: the cases recorded in tests/golden/plotcurves.npz (event lists
+"""Shared by oracle/golden_plotcurves.py and the plot-curve tests: the cases recorded in tests/golden/plotcurves.npz (event lists
 regenerated from seeds, never stored), a driver that replays a case on any object with the widgets' methods, and a numpy
 restatement of the curve formulas and compute_peaks (friture/spectrumPlotWidget.py:122-200, friture/histplot.py:77-130)."""
 from __future__ import annotations

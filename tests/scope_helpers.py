@@ -1,4 +1,4 @@
-"""Shared by tools/make_golden_scope.py and the scope tests: the fixture's cases (signals regenerated from seeds, never stored;
+"""Shared by oracle/golden_scope.py and the scope tests: the fixture's cases (signals regenerated from seeds, never stored;
 chunk schedules; timerange schedules) and a numpy restatement of Scope_Widget.handle_new_data (friture/scope.py:78-135) over
 the zero-padded stream, the form the kernels compute (friture_amd/csrc/scope.hip)."""
 from __future__ import annotations

@@ -1,5 +1,5 @@
 """friture_amd/data/octave_filters.npz holds the reference's design numbers verbatim
-(tools/extract_reference_tables.py); its digest was recorded next to the reference
+(oracle/golden_tables.py); its digest was recorded next to the reference
 (tests/golden/filter_tables.sha256), and our own re-derivation stays close."""
 import hashlib
 from pathlib import Path

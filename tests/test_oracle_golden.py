@@ -1,12 +1,18 @@
-"""The oracle against golden vectors recorded from the unmodified reference (oracle/make_golden.py).
+"""The oracle against golden vectors recorded from the unmodified reference (python -m oracle.make_golden).
 
 These run wherever the tests run — in particular on the GPU box, where the reference checkout does
-not exist — and pin oracle/dsp.py to the reference's outputs for every row of SURVEY.md §8a.
+not exist — and pin oracle/dsp.py to the reference's outputs for every row of SURVEY.md §8a.  Where the
+checkout exists, the last test records every fixture again and compares it with the committed file.
 """
+import re
+import subprocess
+import sys
+from pathlib import Path
+
 import numpy as np
 import pytest
 
-from oracle import dsp
+from oracle import dsp, refshim
 
 
 def f64(x):
@@ -160,7 +166,7 @@ PITCH_SIGNALS = ["steady220", "glide", "jump", "quiet", "noise", "silence", "hig
 @pytest.mark.parametrize("n_fft,hop", PITCH_CASES)
 def test_pitch_tracker(golden, n_fft, hop):
     """T1: table construction and per-frame estimates vs the reference's
-    PitchTracker executed in the build container (oracle/make_golden_pitch.py)."""
+    PitchTracker executed in the build container (oracle/golden_pitch.py)."""
     g = golden("pitch")
     freqs, kernels = dsp.swipe_tables()
     assert np.array_equal(freqs, g["freqs"])
@@ -184,3 +190,20 @@ def test_pitch_upstream_known_answers(golden):
     f0, conf, db = dsp.pitch_candidate(frame, dsp.hann_symmetric(32), freqs, kernels)
     assert f0 == g["kat32_raw"][0]
     assert np.isnan(g["kat32_reference_today"][0]) and np.isnan(dsp.PitchGate().step(f0, conf, db))
+
+
+@pytest.mark.skipif(not refshim.available(), reason="needs the reference checkout (FRITURE_REFERENCE): the recorders execute it")
+def test_committed_fixtures_are_what_the_reference_records():
+    """python -m oracle.make_golden --check: every fixture under tests/golden/ and the filter tables, recorded again from the
+    unmodified reference, equal the committed files array for array (names, dtypes, shapes, values; no tolerance)."""
+    root = Path(__file__).resolve().parents[1]
+    run = subprocess.run([sys.executable, "-m", "oracle.make_golden", "--check"], cwd=root, capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    compared = {m[1]: int(m[2]) for m in re.finditer(r"^(\w+): (\d+) arrays identical$", run.stdout, re.M)}
+    want = {}
+    for p in (root / "tests" / "golden").glob("*.npz"):
+        with np.load(p, allow_pickle=False) as z:
+            want[p.stem] = len(z.files)
+    want["filter_tables"] = len((root / "tests" / "golden" / "filter_tables.sha256").read_text().splitlines())
+    assert len(want) >= 14 and all(want.values())
+    assert compared == want, run.stdout
