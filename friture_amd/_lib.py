@@ -127,6 +127,8 @@ SIGNATURES = {
     "frt_curves_decay_step": (c_double, []),
     "frt_curves_run": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_double, c_double, c_void_p, c_int, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "frt_spectrum_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, POINTER(c_int64), c_int64,
+                                   c_void_p, c_int, c_double, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

@@ -5,14 +5,18 @@ push into the ring, transform every realizable frame (one batched launch of the 
 over the contiguous ring window instead of a Python loop of analyzelive calls), exponential smoothing
 across the new frames, dB + weighting (or the dual-channel ratio), spectral peak and the harmonic
 product spectrum pitch — the last four fused in frt_spectrum_post.
+
+`SpectrumBatch` runs the same chain over whole recordings, many streams at a time, in device calls
+(frt_spectrum_batch, spectrumbatch.hip); its dB rows are what `plotcurves.CurveBatch` reads.
 """
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, tables
 from .audioproc import audioproc
 from .constants import SAMPLING_RATE
 from .ringbuffer import RingBuffer
@@ -186,3 +190,211 @@ class SpectrumAnalyzerStream(SpectrumAnalyzer):
             None if weight is None else vp(weight.data_ptr()), None if ref is None else vp(ref.data_ptr()), vp(self._d_next.data_ptr()),
             self._db.ctypes.data, ctypes.byref(peak), ctypes.byref(pitch)))
         return peak.value, pitch.value
+
+
+# ---- the same chain over whole recordings ---------------------------------------------------------------------------------
+
+class SpectrumState(NamedTuple):
+    """What a spectrum widget carries between two calls: its smoothed spectra, the samples it still needs and how many of them it
+    has received but not consumed."""
+    smoothed: object        # [S, rows, B] float64
+    tail: object            # [S, rows, fft_size + pending] float64: samples [old_index - fft_size, offset), zeros before the start
+    pending: int            # offset - old_index (below hop after a refresh whenever fft_size (1 - overlap) is a whole number)
+
+
+class SpectrumResult(NamedTuple):
+    db: object              # [S, R', B] float64 (R' = R, or 1 with keep="last"); [R', B] for one stream given without its axis
+    peak_index: object      # [S, R'] int32
+    pitch_index: object     # [S, R'] int32
+    fmax: object            # [S, R'] float64: freq[peak_index]
+    fpitch: object          # [S, R'] float64: max(freq[pitch_index], 1e-20)
+    refresh_chunk: object   # [R] int64 (host): the chunk that caused each refresh
+    state: SpectrumState
+
+
+class SpectrumBatch:
+    """S streams of a whole recording through the spectrum widget's chain in device calls, as widgets fed chunk by chunk would
+    have seen it: the float64 STFT engine over the frames the schedule consumes, then frt_spectrum_batch (smoothing, dB +
+    weighting or the dual-channel ratio, peak and harmonic-product pitch per refresh).  Fixed settings, no pause.
+    run(x, chunk=512 | ends=..., state=None, keep="all" | "last") takes [S, T] ([S, 2, T] with dual_channels; the stream axis
+    may be left out for one stream), float32 or float64, numpy array or CUDA tensor.  Results are numpy for numpy input and CUDA
+    tensors for CUDA input; a CUDA `db` is what CurveBatch.run reads in place.  The PSD frames between the two stages live in at
+    most `scratch_bytes` of device memory (or one refresh, if that is larger): longer recordings go through in time slabs, with
+    the same bits whatever the slab size."""
+
+    def __init__(self, fft_size: int = DEFAULT_FFT_SIZE, overlap: float = 3. / 4., weighting: int = 1,
+                 response_time: float = DEFAULT_RESPONSE_TIME, dual_channels: bool = False):
+        self.fft_size = int(fft_size)
+        self.overlap = overlap
+        self.weighting = weighting
+        self.response_time = response_time
+        self.dual_channels = bool(dual_channels)
+        self.rows = 2 if self.dual_channels else 1
+        self.needed = self.fft_size * (1. - overlap)                # a float, as in the widget
+        self.hop = int(self.needed)
+        if self.fft_size < 4 or self.fft_size % 2 or self.hop < 1:
+            raise ValueError(f"fft_size {fft_size} with overlap {overlap}: no frame advance")
+        self.freq = tables.rfft_frequencies(self.fft_size)
+        A, B, C = tables.weighting_db(self.freq, floor=1e-50)
+        self.w = {0: np.zeros(A.shape), 1: A, 2: B}.get(weighting, C)
+        self.n_bins = len(self.freq)
+        w = 0.65                                                    # setresponsetime (spectrum.py:196-222)
+        n = response_time * SAMPLING_RATE / (self.fft_size * (1. - overlap))
+        self.alpha = 1. - (1. - w) ** (1. / (n + 1))
+        self.kernel = (1. - self.alpha) ** np.arange(2 * 4096 - 1, -1, -1)
+        self._engines = {}
+        self._dev_tables = {}
+
+    # ---- host only ------------------------------------------------------------------------------------------------------------
+    def schedule(self, n_samples, chunk=512, ends=None, state=None):
+        """(frame_start [R + 1], refresh_chunk [R]) of a stream of n_samples seen chunk by chunk (`ends`: the chunks' end indices,
+        for ragged chunks; default: the ends of `chunk`-sample chunks, a short last chunk is a short chunk).  Refresh r consumes
+        the frames frame_start[r] .. frame_start[r + 1] - 1; frame j is the fft_size samples ending at j * hop - pending, zeros
+        before the stream's start, so a fresh widget's frame 0 is all zeros."""
+        n_samples = int(n_samples)
+        if ends is None:
+            if chunk < 1:
+                raise ValueError(f"chunk {chunk}")
+            ends = np.minimum(np.arange(1, -(-n_samples // chunk) + 1, dtype=np.int64) * chunk, n_samples)
+        else:
+            ends = np.asarray(ends, np.int64).reshape(-1)
+            if ends.size and (ends[0] < 0 or ends[-1] > n_samples or np.any(np.diff(ends) < 0)):
+                raise ValueError(f"ends must be sorted and within [0, {n_samples}]")
+        old_index = -(0 if state is None else int(state.pending))
+        frame_start, refresh_chunk = [0], []
+        for c, e in enumerate(ends.tolist()):
+            realizable = int(np.floor((e - old_index) / self.needed))
+            if realizable > 0:
+                frame_start.append(frame_start[-1] + realizable)
+                refresh_chunk.append(c)
+                old_index += realizable * self.hop
+        return np.array(frame_start, np.int64), np.array(refresh_chunk, np.int64)
+
+    # ---- device ---------------------------------------------------------------------------------------------------------------
+    def _check_input(self, x, state):
+        is_np = isinstance(x, np.ndarray)
+        if not is_np and not (type(x).__module__.startswith("torch") and x.is_cuda):
+            raise TypeError("SpectrumBatch.run takes a numpy array or a CUDA tensor")
+        full = 3 if self.dual_channels else 2
+        if x.ndim not in (full - 1, full):
+            raise ValueError(f"expected [S, {'2, ' if self.dual_channels else ''}T] (the stream axis may be left out), got {tuple(x.shape)}")
+        if str(x.dtype).split(".")[-1] not in ("float32", "float64"):
+            raise TypeError(f"samples must be float32 or float64, got {x.dtype}")
+        squeeze = x.ndim == full - 1
+        if squeeze:
+            x = x[None]
+        if self.dual_channels and x.shape[1] != 2:
+            raise ValueError(f"dual channels need two rows per stream, got {x.shape[1]}")
+        S, T = x.shape[0], x.shape[-1]
+        pending = 0
+        if state is not None:
+            pending = int(state.pending)
+            want_sm, want_tail = (S, self.rows, self.n_bins), (S, self.rows, self.fft_size + pending)
+            if pending < 0 or tuple(state.smoothed.shape) != want_sm or tuple(state.tail.shape) != want_tail:
+                raise ValueError(f"state of another shape: smoothed {tuple(state.smoothed.shape)} (want {want_sm}), tail "
+                                 f"{tuple(state.tail.shape)} (want {want_tail}), pending {pending}")
+        return x, is_np, squeeze, S, T, pending
+
+    def run(self, x, chunk=512, ends=None, state=None, keep="all", scratch_bytes=1 << 30):
+        if keep not in ("all", "last"):
+            raise ValueError(f"keep={keep!r} ('all' or 'last')")
+        x, is_np, squeeze, S, T, pending = self._check_input(x, state)
+        frame_start, refresh_chunk = self.schedule(T, chunk, ends, state)
+        if ends is not None:                                        # the widgets were pushed ends[-1] samples
+            T = int(np.asarray(ends).reshape(-1)[-1]) if np.size(ends) else 0
+        import torch
+        lib = _lib.init()
+        dev = torch.device("cuda", torch.cuda.current_device()) if is_np else x.device
+        rows, B, N, hop = self.rows, self.n_bins, self.fft_size, self.hop
+        C, R, F, L = S * rows, len(refresh_chunk), int(frame_start[-1]), N + pending
+        f64, vp = torch.float64, ctypes.c_void_p
+        # frt_spectrum_batch launches on the null stream (friture_hip.h): everything here is enqueued there, after whatever the
+        # caller's stream still has to do to x
+        mine, null = torch.cuda.current_stream(dev), torch.cuda.default_stream(dev)
+        if mine != null:
+            mine.synchronize()
+        with torch.cuda.device(dev), torch.cuda.stream(null):
+            xd = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) if is_np else x).reshape(C, x.shape[-1])
+            if xd.stride(1) != 1:
+                xd = xd.contiguous()
+            if state is None:
+                sm = torch.zeros((S, rows, B), dtype=f64, device=dev)
+                tail = torch.zeros((C, L), dtype=f64, device=dev)
+            else:                                                    # copies: the caller's state is not modified
+                sm = torch.as_tensor(state.smoothed).to(device=dev, dtype=f64).reshape(S, rows, B).clone()
+                tail = torch.as_tensor(state.tail).to(device=dev, dtype=f64).reshape(C, L).contiguous()
+
+            def window(a, b):
+                """Samples [a, b) of tail || x per row as float64 (float32 widens exactly), unit stride along time."""
+                if a >= L and xd.dtype == f64:
+                    return xd[:, a - L:b - L]
+                out = torch.empty((C, b - a), dtype=f64, device=dev)
+                if a < L:
+                    out[:, :min(b, L) - a] = tail[:, a:min(b, L)]
+                if b > L:
+                    out[:, max(a, L) - a:] = xd[:, max(a, L) - L:b - L]
+                return out
+
+            Ro = R if keep == "all" else min(R, 1)
+            db = torch.empty((S, Ro, B), dtype=f64, device=dev)
+            peak = torch.empty((S, Ro), dtype=torch.int32, device=dev)
+            pitch = torch.empty((S, Ro), dtype=torch.int32, device=dev)
+            if R:
+                wd = None if self.dual_channels else self._table(dev, "w", self.w)
+                eng = self._engine(C)
+                _lib.check(lib.frt_stft_set_stream(eng._h, None))
+                # time slabs: whole refreshes, at most fmax frames of PSD each (one refresh if it alone has more)
+                fmax = max(1, int(scratch_bytes) // (C * B * 8))
+                slabs, r0 = [], 0
+                while r0 < R:
+                    r1 = max(r0 + 1, int(np.searchsorted(frame_start, frame_start[r0] + fmax, "right")) - 1)
+                    slabs.append((r0, r1))
+                    r0 = r1
+                psd = torch.empty(C * B * max(int(frame_start[b] - frame_start[a]) for a, b in slabs), dtype=f64, device=dev)
+                nfo = ctypes.c_int64(0)
+                for r0, r1 in slabs:
+                    fa, fb = int(frame_start[r0]), int(frame_start[r1])
+                    nf, nr = fb - fa, r1 - r0
+                    seg = window(fa * hop, (fb - 1) * hop + N)
+                    _lib.check(lib.frt_stft_run(eng._h, _lib.FRT_STFT_PSD, vp(seg.data_ptr()), seg.shape[1], seg.stride(0) if C > 1 else seg.shape[1],
+                                                vp(psd.data_ptr()), ctypes.byref(nfo)))
+                    assert nfo.value == nf
+                    local = np.ascontiguousarray(frame_start[r0:r1 + 1] - fa)
+                    if keep == "all":
+                        pk = torch.empty((S, nr), dtype=torch.int32, device=dev)
+                        pt = torch.empty((S, nr), dtype=torch.int32, device=dev)
+                        dbp, ld_db = db.data_ptr() + r0 * B * 8, R * B
+                    else:
+                        pk, pt, dbp, ld_db = peak, pitch, db.data_ptr(), 0
+                    _lib.check(lib.frt_spectrum_batch(
+                        vp(psd.data_ptr()), 1, S, rows, nf, B, B, nf * B, local.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nr,
+                        self.kernel.ctypes.data, len(self.kernel), float(self.alpha), None if wd is None else vp(wd.data_ptr()),
+                        vp(sm.data_ptr()), int(keep == "last"), vp(dbp), ld_db, vp(pk.data_ptr()), vp(pt.data_ptr())))
+                    if keep == "all":
+                        peak[:, r0:r1], pitch[:, r0:r1] = pk, pt
+                del psd
+            new_tail = window(F * hop, L + T).clone().reshape(S, rows, L + T - F * hop)
+            new_state = SpectrumState(sm, new_tail, L + T - F * hop - N)
+            if is_np:
+                db, peak, pitch = db.cpu().numpy(), peak.cpu().numpy(), pitch.cpu().numpy()
+                fmax_hz, fpitch_hz = self.freq[peak], np.maximum(self.freq[pitch], 1e-20)
+                new_state = SpectrumState(sm.cpu().numpy(), new_tail.cpu().numpy(), new_state.pending)
+            else:
+                fd = self._table(dev, "freq", self.freq)
+                fmax_hz, fpitch_hz = fd[peak.long()], torch.clamp_min(fd[pitch.long()], 1e-20)
+        if mine != null:
+            null.synchronize()
+        if squeeze:
+            db, peak, pitch, fmax_hz, fpitch_hz = db[0], peak[0], pitch[0], fmax_hz[0], fpitch_hz[0]
+        return SpectrumResult(db, peak, pitch, fmax_hz, fpitch_hz, refresh_chunk, new_state)
+
+    def _engine(self, channels):
+        if channels not in self._engines:
+            self._engines[channels] = StftEngine(self.fft_size, self.hop, channels, 64)
+        return self._engines[channels]
+
+    def _table(self, dev, name, values):
+        import torch
+        if (dev, name) not in self._dev_tables:
+            self._dev_tables[(dev, name)] = torch.from_numpy(np.ascontiguousarray(values, np.float64)).to(dev)
+        return self._dev_tables[(dev, name)]

@@ -466,6 +466,27 @@ int frt_curves_run(const void* y, int dtype, int streams, int64_t n_refresh, int
                    double cmin, double cmax, double* state, int peaks, int keep_last, double* scaled_y, double* z,
                    double* scaled_peak, double* z_peak);
 
+/* ---- P2: the spectrum widget's chain over whole recordings (Spectrum_Widget.handle_new_data, friture/spectrum.py:125-184) ----
+ * Between the float64 STFT engine and frt_curves_run: per refresh r of stream s, which owns the PSD frames
+ * frame_start[r] .. frame_start[r + 1] - 1 (n of them, accumulated in frame order; friture/signal/exp_smoothing.py:91-107):
+ *   sp = alpha * sum_t psd[t] * kernel[nk - n + t] + previous * (1 - alpha)^n      (n > nk: the first nk frames, decay 0)
+ *   dB = 10 log10(sp + 1e-30) + weight_db   (rows == 2, dual channels: 10 log10(sp2 + 1e-30) - 10 log10(sp1 + 1e-30), no weight)
+ *   peak = argmax(dB);  pitch = argmax(sp1[k] sp1[2k] sp1[3k], k < bins / 3)   (spectrum.py:103-123); first index wins ties; NaNs
+ *   are skipped (PSD >= 0 is the precondition)
+ * Refreshes are walked in time order and each (stream, row, bin) is a fixed sequence of IEEE operations: a recording cut into
+ * several calls with the state carried gives the same bits as one call.
+ * psd: psd[(s * rows + row) * ld_row + f * ld_frame + b], float32 (dtype 0) or float64 (dtype 1), host or device — the slab
+ * frt_stft_run leaves (ld_frame = bins, ld_row = n_frames * bins).  frame_start: [n_refresh + 1] HOST int64, sorted, within
+ * [0, n_frames].  kernel: [nk] HOST doubles, (1 - alpha)^(nk - 1 .. 0).  weight_db: [bins] or NULL.  state: [streams][rows][bins]
+ * smoothed spectra, read and written.  db_out: [streams][R'][bins] with R' = n_refresh, or 1 with keep_last (the final refresh;
+ * the state still walks every refresh); stream s starts at s * ld_db_stream (0 = packed; a padded layout needs a device
+ * output).  peak_index_out, pitch_index_out: [streams][R'].  Host or device buffers in any mix; launched on the null stream when
+ * any buffer is in device memory (STREAM ORDER as for frt_spectrum_post); one synchronisation at the end. */
+int frt_spectrum_batch(const void* psd, int dtype, int streams, int rows, int64_t n_frames, int64_t bins, int64_t ld_frame,
+                       int64_t ld_row, const int64_t* frame_start, int64_t n_refresh, const double* kernel, int nk, double alpha,
+                       const double* weight_db, double* state, int keep_last, double* db_out, int64_t ld_db_stream,
+                       int* peak_index_out, int* pitch_index_out);
+
 #ifdef __cplusplus
 }
 #endif
