@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "widget_device.h"
 
 namespace frt {
 namespace {
@@ -48,13 +49,6 @@ struct CurvesParams {
     double *sy, *z, *sp, *zp;       // [streams][Ro][B] or null
 };
 
-__device__ __forceinline__ double nanmax(double a, double b) { return (a > b || a != a) ? a : b; }   // numpy.max: NaN wins
-
-template <bool kF64>
-__device__ __forceinline__ double load_y(const void* base, long long i) {
-    return kF64 ? reinterpret_cast<const double*>(base)[i] : (double)reinterpret_cast<const float*>(base)[i];
-}
-
 __device__ __forceinline__ double screen_from_top(const CurvesParams& p, double v) {   // 1. - toScreen(v)
     const double t = p.flat ? 0. + 0. * v : (v - p.cmin) / (p.cmax - p.cmin);
     return 1. - t;
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void curves_rowmax_kernel(CurvesParams p)
         const long long r = p.Ro == p.R ? j : p.R - 1;
         const long long off = s * p.ld_stream + r * p.ld_refresh;
 #pragma unroll 8
-        for (long long b = sub; b < p.B; b += G) m = nanmax(m, load_y<kF64>(p.y, off + b));
+        for (long long b = sub; b < p.B; b += G) m = nanmax(m, load_real<kF64>(p.y, off + b));
     }
     for (int o = 1; o < G; o <<= 1) m = nanmax(m, __shfl_xor(m, o, 64));
     if (row < rows && sub == 0) p.rowmax[row] = m;
@@ -125,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void curves_scan_kernel(CurvesParams p) {
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
             const long long r = r0 + u < R ? r0 + u : R - 1;
-            yv[u] = load_y<kF64>(yb, r * p.ld_refresh);
+            yv[u] = load_real<kF64>(yb, r * p.ld_refresh);
             mv[u] = need_m ? mrow[r] : Mlast;
         }
     };

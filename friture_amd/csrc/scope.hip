@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "widget_device.h"
 
 namespace frt {
 namespace {
@@ -54,21 +55,14 @@ struct ScopeParams {
     const double* keep_scaled;
 };
 
-__device__ __forceinline__ double nanmax(double a, double b) { return (a > b || a != a) ? a : b; }   // numpy.max: NaN wins
-
 __device__ __forceinline__ double load(const ScopeParams& p, const char* row, long long t) {
     if (t < 0) return 0.0;                                          // before the stream's start: a fresh ring's zeros
-    return p.dtype ? reinterpret_cast<const double*>(row)[t] : (double)reinterpret_cast<const float*>(row)[t];
+    return p.dtype ? load_real<true>(row, t) : load_real<false>(row, t);
 }
 
 __device__ __forceinline__ const char* row_ptr(const ScopeParams& p, int s, int r) {
     const size_t es = p.dtype ? sizeof(double) : sizeof(float);
     return reinterpret_cast<const char*>(p.x) + ((size_t)s * p.ld_stream + (size_t)r * p.ld_row) * es;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = nanmax(v, __shfl_xor(v, o, 64));
-    return v;
 }
 
 __device__ __forceinline__ long long end_of(const ScopeParams& p, long long k) {

@@ -11,19 +11,11 @@
 #include <cmath>
 
 #include "common.h"
+#include "widget_device.h"
 
 namespace frt {
 
 constexpr int kPostThreads = 1024;
-
-struct ArgMax {
-    double v;
-    int i;
-};
-
-__device__ __forceinline__ ArgMax better(ArgMax a, ArgMax b) {          // first index wins ties (numpy.argmax)
-    return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-}
 
 __device__ ArgMax block_argmax(ArgMax m, double* red, int* redi) {
     for (int o = 32; o > 0; o >>= 1) {

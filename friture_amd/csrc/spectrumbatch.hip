@@ -21,29 +21,13 @@
 #include <vector>
 
 #include "common.h"
+#include "widget_device.h"
 
 namespace frt {
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kNone = 0x7fffffff;
-
-struct ArgMax {
-    double v;
-    int i;
-};
-
-__device__ __forceinline__ ArgMax better(ArgMax a, ArgMax b) {          // first index wins ties (numpy.argmax)
-    return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-}
-
-__device__ __forceinline__ ArgMax wave_argmax(ArgMax m) {
-    for (int o = 32; o > 0; o >>= 1) {
-        ArgMax other = {__shfl_xor(m.v, o, 64), __shfl_xor(m.i, o, 64)};
-        m = better(m, other);
-    }
-    return m;
-}
 
 struct BatchParams {
     long long ld_frame, ld_row;     // psd[(s * rows + row) * ld_row + f * ld_frame + b]
@@ -61,18 +45,13 @@ struct BatchParams {
     int* part_i;
 };
 
-template <bool kF64>
-__device__ __forceinline__ double load_psd(const void* base, long long i) {
-    return kF64 ? reinterpret_cast<const double*>(base)[i] : (double)reinterpret_cast<const float*>(base)[i];
-}
-
 // one refresh of one bin: frames f0 .. f0 + n - 1 of `col` (the bin's column of one row), taps kt[0 .. n - 1]
 template <bool kF64>
 __device__ __forceinline__ double smooth(const void* col, long long ld_frame, long long f0, int n, const double* __restrict__ kt,
                                          double alpha, double previous, double decay) {
     double acc = 0.0;
 #pragma unroll 4
-    for (int t = 0; t < n; ++t) acc += load_psd<kF64>(col, (f0 + t) * ld_frame) * kt[t];
+    for (int t = 0; t < n; ++t) acc += load_real<kF64>(col, (f0 + t) * ld_frame) * kt[t];
     return alpha * acc + previous * decay;
 }
 

@@ -10,7 +10,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _batchio, _lib
 from .constants import SAMPLING_RATE
 
 SMOOTH_DISPLAY_TIMER_PERIOD_MS = 25        # levels.py:30
@@ -152,27 +152,18 @@ class LevelsBatch:
 
     def run(self, x, meters=True, long=True):
         h = self._h
-        if isinstance(x, np.ndarray):
-            assert x.ndim == 2 and x.shape[0] == self.channels and x.dtype in (np.float32, np.float64)
-            x = np.ascontiguousarray(x)
-            n = x.shape[1]
-            nb = h.blocks_for(n) if long else 0
-            m = np.empty((self.channels, -(-n // self.chunk), FIELDS)) if meters else None
-            lo = np.empty((self.channels, nb, 2)) if long else None
-            ptr, mp, lp = x.ctypes.data, (m.ctypes.data if meters else None), (lo.ctypes.data if long else None)
-        else:
+        assert x.ndim == 2 and x.shape[0] == self.channels
+        x, ptr, dtype, _ = _batchio.source(x, strided=False)
+        n = x.shape[1]
+        nb = h.blocks_for(n) if long else 0
+        m = _batchio.alloc(x, (self.channels, -(-n // self.chunk), FIELDS)) if meters else None
+        lo = _batchio.alloc(x, (self.channels, nb, 2)) if long else None
+        if not isinstance(x, np.ndarray):
             import torch
-            assert x.is_cuda and x.dim() == 2 and x.shape[0] == self.channels and x.dtype in (torch.float32, torch.float64)
-            x = x.contiguous()
-            n = x.shape[1]
-            nb = h.blocks_for(n) if long else 0
-            m = torch.empty((self.channels, -(-n // self.chunk), FIELDS), dtype=torch.float64, device=x.device) if meters else None
-            lo = torch.empty((self.channels, nb, 2), dtype=torch.float64, device=x.device) if long else None
-            ptr, mp, lp = x.data_ptr(), (m.data_ptr() if meters else None), (lo.data_ptr() if long else None)
             _lib.check(h.lib.frt_levels_set_stream(h.h, ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
-        dtype = 0 if x.dtype in (np.float32,) or str(x.dtype) == "torch.float32" else 1
         got = ctypes.c_int64(0)
-        _lib.check(h.lib.frt_levels_run(h.h, ptr if n else None, dtype, n, n, self.chunk, mp, lp, ctypes.byref(got)))
+        _lib.check(h.lib.frt_levels_run(h.h, ptr if n else None, dtype, n, n, self.chunk, _batchio.ptr(m), _batchio.ptr(lo),
+                                        ctypes.byref(got)))
         assert got.value == nb
         return m, lo
 

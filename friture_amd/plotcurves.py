@@ -13,7 +13,8 @@ from typing import NamedTuple
 
 import numpy as np
 
-from . import _lib
+from . import _batchio, _lib
+from ._batchio import ptr as _ptr
 from .constants import SAMPLING_RATE
 from .plotting import frequency_scales as fscales
 
@@ -96,12 +97,6 @@ def initial_state(bins, streams=None):
         return reset_state(bins, streams)
     st = np.array([np.zeros(3), np.zeros(3), np.ones(3) * PEAK_DECAY_RATE])
     return st if streams is None else np.repeat(st[None], streams, axis=0)
-
-
-def _ptr(a):
-    if a is None:
-        return None
-    return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
 
 
 def _run(y, dtype, S, R, B, ld_r, ld_s, cmin, cmax, state, peaks, keep_last, sy, z, sp, zp):
@@ -260,20 +255,11 @@ class CurveBatch:
             y = y[None]
         S, R, B = y.shape
         Ro = R if keep == "all" else 1
+        y, ptr, dtype, (ld_s, ld_r, _) = _batchio.source(y, strided=True)
         if isinstance(y, np.ndarray):
-            assert y.dtype in (np.float32, np.float64)
-            if y.strides[2] != y.itemsize or any(st % y.itemsize or st < 0 for st in y.strides):
-                y = np.ascontiguousarray(y)
-            ptr, dtype = y.ctypes.data, int(y.dtype == np.float64)
-            ld_r, ld_s = y.strides[1] // y.itemsize, y.strides[0] // y.itemsize
             st = initial_state(B, S) if state is None else np.array(np.asarray(state).reshape(S, 3, B), np.float64, copy=True)
-            outs = [np.empty((S, Ro, B)) for _ in range(4)]
         else:
             import torch
-            assert y.is_cuda and y.dtype in (torch.float32, torch.float64)
-            if y.stride(2) != 1:
-                y = y.contiguous()
-            ptr, dtype, ld_r, ld_s = y.data_ptr(), int(y.dtype == torch.float64), y.stride(1), y.stride(0)
             if state is None:                           # built on the device: nothing goes up
                 st = torch.empty((S, 3, B), dtype=torch.float64, device=y.device)
                 fresh = initial_state(B)
@@ -281,7 +267,7 @@ class CurveBatch:
                     st[:, i] = float(fresh[i, 0])
             else:
                 st = torch.as_tensor(state, dtype=torch.float64).to(y.device).reshape(S, 3, B).clone()
-            outs = [torch.empty((S, Ro, B), dtype=torch.float64, device=y.device) for _ in range(4)]
+        outs = [_batchio.alloc(y, (S, Ro, B)) for _ in range(4)]
         _run(ptr, dtype, S, R, B, ld_r, ld_s, self.spec_min, self.spec_max, st, True, keep == "last", *outs)
         if squeeze:
             outs, st = [o[0] for o in outs], st[0]

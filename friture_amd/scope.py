@@ -12,7 +12,8 @@ from typing import NamedTuple
 
 import numpy as np
 
-from . import _lib
+from . import _batchio, _lib
+from ._batchio import chunk_ends
 from .constants import SAMPLING_RATE
 
 SMOOTH_DISPLAY_TIMER_PERIOD_MS = 25                   # scope.py:30
@@ -41,11 +42,6 @@ def time_axis(width, timerange, length):
     """scope.py:126-128: (time, scaled_t) of a trace of `length` samples; depends only on the width and the timerange."""
     time = (np.arange(length) - width // 2) / float(SAMPLING_RATE)
     return time, (time * 1e3 + timerange / 2.) / timerange
-
-
-def chunk_ends(T, chunk=512):
-    """The stream ends at which a widget fed `chunk`-sample chunks refreshes (a short last chunk is a short chunk)."""
-    return np.minimum(np.arange(1, -(-T // chunk) + 1, dtype=np.int64) * chunk, T)
 
 
 def _run(x, dtype, streams, rows, n, ld_row, ld_stream, ends, width, scrolling, start, trace, kind):
@@ -163,21 +159,11 @@ class ScopeBatch:
         ends = chunk_ends(T, chunk) if ends is None else np.asarray(ends, np.int64)
         K, L = ends.shape[0], self.length
         if isinstance(x, np.ndarray):
-            assert x.dtype in (np.float32, np.float64)
-            x = np.ascontiguousarray(x)
-            ptr, dtype, ld_row, ld_stream = x.ctypes.data, int(x.dtype == np.float64), T, C * T
-            starts = np.empty((S, K), np.int64)
-            tr = np.zeros((S, C, K, L)) if kind else None
-            sp, tp = starts.ctypes.data, (tr.ctypes.data if kind else None)
-        else:
-            import torch
-            assert x.is_cuda and x.dtype in (torch.float32, torch.float64)
-            if x.stride(2) != 1:
-                x = x.contiguous()
-            ptr, dtype, ld_row, ld_stream = x.data_ptr(), int(x.dtype == torch.float64), x.stride(1), x.stride(0)
-            starts = torch.empty((S, K), dtype=torch.int64, device=x.device)
-            tr = torch.zeros((S, C, K, L), dtype=torch.float64, device=x.device) if kind else None
-            sp, tp = starts.data_ptr(), (tr.data_ptr() if kind else None)
+            x = np.ascontiguousarray(x)                  # host input is staged whole; a CUDA tensor's rows may stay strided
+        x, ptr, dtype, (ld_stream, ld_row, _) = _batchio.source(x, strided=True)
+        starts = _batchio.alloc(x, (S, K), np.int64)
+        tr = _batchio.alloc(x, (S, C, K, L), zero=True) if kind else None
+        sp, tp = _batchio.ptr(starts), _batchio.ptr(tr)
         _run(ptr if T else None, dtype, S, C, T, ld_row, ld_stream, ends, self.width, self.scrolling, sp, tp, kind)
         trig = starts != NO_TRIGGER
         if squeeze:

@@ -17,6 +17,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _lib, tables
+from ._batchio import chunk_ends
 from .audioproc import audioproc
 from .constants import SAMPLING_RATE
 from .ringbuffer import RingBuffer
@@ -24,6 +25,20 @@ from .stft import StftEngine
 
 DEFAULT_FFT_SIZE = 8192         # spectrum_settings.py:27-37
 DEFAULT_RESPONSE_TIME = 0.025
+
+
+def smoothing_setup(fft_size, overlap, response_time):
+    """(alpha, kernel) of setresponsetime (spectrum.py:196-222)."""
+    w = 0.65
+    n = response_time * SAMPLING_RATE / (fft_size * (1. - overlap))
+    alpha = 1. - (1. - w) ** (1. / (n + 1))
+    return alpha, (1. - alpha) ** np.arange(2 * 4096 - 1, -1, -1)
+
+
+def weighting_row(curves, weighting):
+    """The dB row that `weighting` (0 none, 1 A, 2 B, else C) adds, from the (A, B, C) curves."""
+    A, B, C = curves
+    return {0: np.zeros(A.shape), 1: A, 2: B}.get(weighting, C)
 
 
 class SpectrumAnalyzer:
@@ -55,21 +70,19 @@ class SpectrumAnalyzer:
 
     def setresponsetime(self, response_time):
         self.response_time = response_time
-        w = 0.65
-        n = response_time * SAMPLING_RATE / (self.fft_size * (1. - self.overlap))
-        self.alpha = 1. - (1. - w) ** (1. / (n + 1))
-        self.kernel = (1. - self.alpha) ** np.arange(2 * 4096 - 1, -1, -1)
+        self.alpha, self.kernel = smoothing_setup(self.fft_size, self.overlap, response_time)
 
     def setweighting(self, weighting):
         self.weighting = weighting
         self.update_weighting()
 
     def update_weighting(self):
-        A, B, C = self.proc.get_freq_weighting()
-        self.w = {0: np.zeros(A.shape), 1: A, 2: B}.get(self.weighting, C)
+        self.w = weighting_row(self.proc.get_freq_weighting(), self.weighting)
 
     # ---- the slot -------------------------------------------------------------------------------------
-    def handle_new_data(self, floatdata):
+    def _push(self, floatdata):
+        """The ring push and the frame bookkeeping of the slot: (window, realizable) with `window` the ring's samples of the
+        `realizable` new frames, or None while no frame completes."""
         self.ringbuffer.push(floatdata, 0.)
         index = self.ringbuffer.offset
         available = index - self.old_index
@@ -85,6 +98,13 @@ class SpectrumAnalyzer:
         last = self.old_index + (realizable - 1) * self.hop
         window = self.ringbuffer.data_indexed(last, span)
         self.old_index += realizable * self.hop
+        return window, realizable
+
+    def handle_new_data(self, floatdata):
+        new = self._push(floatdata)
+        if new is None:
+            return None
+        window, _ = new
         sp1, db, peak, pitch = self._post(self._engine.psd(window[0:1, :].copy())[0], self.dispbuffers1, self.w, None)
         self.dispbuffers1 = sp1
         if self.dual_channels and window.shape[0] > 1:
@@ -139,20 +159,10 @@ class SpectrumAnalyzerStream(SpectrumAnalyzer):
         self._d_w = self._torch.from_numpy(np.ascontiguousarray(self.w, np.float64)).to(self._dev)
 
     def handle_new_data(self, floatdata):
-        self.ringbuffer.push(floatdata, 0.)
-        index = self.ringbuffer.offset
-        available = index - self.old_index
-        if available < 0:
-            available = 0
-            self.old_index = index
-        needed = self.fft_size * (1. - self.overlap)
-        realizable = int(np.floor(available / needed))
-        if realizable <= 0:
+        new = self._push(floatdata)
+        if new is None:
             return None
-        span = self.fft_size + (realizable - 1) * self.hop
-        last = self.old_index + (realizable - 1) * self.hop
-        window = self.ringbuffer.data_indexed(last, span)
-        self.old_index += realizable * self.hop
+        window, realizable = new
         peak, pitch = self._post_dev(self._psd_dev(window[0], realizable), self._d_disp1, self._d_w, None)
         self._d_disp1, self._d_next = self._d_next, self._d_disp1
         if self.dual_channels and window.shape[0] > 1:
@@ -235,13 +245,9 @@ class SpectrumBatch:
         if self.fft_size < 4 or self.fft_size % 2 or self.hop < 1:
             raise ValueError(f"fft_size {fft_size} with overlap {overlap}: no frame advance")
         self.freq = tables.rfft_frequencies(self.fft_size)
-        A, B, C = tables.weighting_db(self.freq, floor=1e-50)
-        self.w = {0: np.zeros(A.shape), 1: A, 2: B}.get(weighting, C)
+        self.w = weighting_row(tables.weighting_db(self.freq, floor=1e-50), weighting)
         self.n_bins = len(self.freq)
-        w = 0.65                                                    # setresponsetime (spectrum.py:196-222)
-        n = response_time * SAMPLING_RATE / (self.fft_size * (1. - overlap))
-        self.alpha = 1. - (1. - w) ** (1. / (n + 1))
-        self.kernel = (1. - self.alpha) ** np.arange(2 * 4096 - 1, -1, -1)
+        self.alpha, self.kernel = smoothing_setup(self.fft_size, overlap, response_time)
         self._engines = {}
         self._dev_tables = {}
 
@@ -255,7 +261,7 @@ class SpectrumBatch:
         if ends is None:
             if chunk < 1:
                 raise ValueError(f"chunk {chunk}")
-            ends = np.minimum(np.arange(1, -(-n_samples // chunk) + 1, dtype=np.int64) * chunk, n_samples)
+            ends = chunk_ends(n_samples, chunk)
         else:
             ends = np.asarray(ends, np.int64).reshape(-1)
             if ends.size and (ends[0] < 0 or ends[-1] > n_samples or np.any(np.diff(ends) < 0)):

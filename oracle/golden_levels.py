@@ -1,7 +1,7 @@
 """Record levels.npz from the reference's own Levels_Widget, LongLevelWidget and Subsampler.
 
 Driven by oracle/make_golden.py (needs the reference checkout): the stand-ins of oracle/refshim.py plus the two settings
-dialogs, then the reference classes are driven chunk by chunk on the signals of tests/levels_helpers.py (regenerated from seeds
+dialogs, then the reference classes are driven chunk by chunk on the signals of oracle/levels.py (regenerated from seeds
 there, never stored).  Recorded per meter step: rms, old_max, level_rms, level_max, peak_iec, the BallisticPeak branch (0 follow, 1 hold,
 2 decay, 3 decay below the input) and the margins of its comparisons; per long-level block: level and dB; the Subsampler's
 outputs; the curves handed to Curve.setData around setduration / setmin / setmax / setresptime; the coefficients.
@@ -13,9 +13,8 @@ import types
 
 import numpy as np
 
+from . import levels as H
 from . import refshim
-
-import levels_helpers as H  # noqa: E402  (tests/ is on sys.path once refshim is imported)
 
 
 def install_stubs():

@@ -2,9 +2,9 @@
 
 Driven by oracle/make_golden.py (needs the reference checkout): the stand-ins of oracle/refshim.py plus FilledCurve,
 Spectrum_Data / HistPlot_Data and format_frequency without the pitch tracker's widget stack, then the reference classes replay
-the cases of tests/plotcurves_helpers.py (inputs regenerated from seeds there, never stored).  Recorded per data event: whether setdata drew, whether the peak curve was set, the baseline, the fmax / fpitch labels
+the cases of oracle/plotcurves.py (inputs regenerated from seeds there, never stored).  Recorded per data event: whether setdata drew, whether the peak curve was set, the baseline, the fmax / fpitch labels
 (text and screen position), and digests of every array handed to FilledCurve.setData and setBarLabels and of the peak state
-afterwards; the whole arrays of a few refreshes (tests/plotcurves_helpers.FULL_REFRESHES).
+afterwards; the whole arrays of a few refreshes (oracle.plotcurves.FULL_REFRESHES).
 """
 from __future__ import annotations
 
@@ -12,9 +12,8 @@ import enum
 
 import numpy as np
 
+from . import plotcurves as H
 from . import refshim
-
-import plotcurves_helpers as H  # noqa: E402  (tests/ is on sys.path once refshim is imported)
 
 DIG = ["sxl", "sxr", "sy", "z", "sp", "zp", "peak", "pint", "pdecay", "barx"]
 

@@ -1,11 +1,11 @@
 """Record scope.npz from the reference's own Scope_Widget.
 
 Driven by oracle/make_golden.py (needs the reference checkout): on the stand-ins of oracle/refshim.py, the reference class is
-driven chunk by chunk through the reference RingBuffer on the cases of tests/scope_helpers.py (signals regenerated from seeds
+driven chunk by chunk through the reference RingBuffer on the cases of oracle/scope.py (signals regenerated from seeds
 there, never stored).  Recorded per refresh: whether Curve.setData ran (the trigger), the absolute index
 of the trace's first sample (read from the view the widget cut out of the ring's window), the trace length, whether the window
 the widget read equals the zero-padded stream, and a digest of the data each curve holds afterwards; the whole setData arrays
-of a few refreshes (tests/scope_helpers.FULL_REFRESHES), among them the refresh whose data(2 w) grows the ring
+of a few refreshes (oracle.scope.FULL_REFRESHES), among them the refresh whose data(2 w) grows the ring
 and one that scrolls over what the growth left.
 """
 from __future__ import annotations
@@ -13,8 +13,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import refshim
-
-import scope_helpers as H  # noqa: E402  (tests/ is on sys.path once refshim is imported)
+from . import scope as H
 
 
 def _curve_data(curve):

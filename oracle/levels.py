@@ -1,12 +1,12 @@
-"""Shared by oracle/golden_levels.py and the level tests: the fixture's input signals (regenerated from seeds, never
+"""The level meters' cases and CPU restatement, shared by oracle/golden_levels.py and the level tests: the fixture's input signals (regenerated from seeds, never
 stored) and a numpy restatement of the long-level path as raw-input tap sums — the form the kernels compute
 (friture_amd/csrc/levels.hip): y[n] = ((x[n-10] b10 + x[n-9] b9) + ...) + x[n] b0, elementwise IEEE operations."""
 from __future__ import annotations
 
 import numpy as np
 
-FS = 48000
-CHUNK = 512
+from .cases import CHUNK, FS, chunk_ends
+
 SUBSAMPLER_PUSHES = [0, 5, 1, 11, 3, 1000, 0, 7, 513, 2049, 10, 1, 4096, 9, 8191, 2, 333, 16384, 1, 0, 77]
 IRREGULAR_CHUNKS = [512, 0, 7, 1, 10, 513, 2048, 0, 300, 4099, 1, 8192, 65, 11, 9000, 512, 0, 3, 20000, 255]
 CURVE_STEPS = [("push", 40), ("setduration", 10), ("push", 20), ("setmin", -50), ("push", 20), ("setmax", -10), ("push", 20),
@@ -49,13 +49,8 @@ def signal(name):
 
 def chunks(T, sizes=None):
     """[(start, length)] of a case: CHUNK-sample chunks (short last one), or the given sizes."""
-    if sizes is None:
-        return [(s, min(CHUNK, T - s)) for s in range(0, T, CHUNK)]
-    out, s = [], 0
-    for n in sizes:
-        out.append((s, n))
-        s += n
-    return out
+    ends = chunk_ends(T) if sizes is None else np.cumsum(sizes)
+    return [(int(e - n), int(n)) for e, n in zip(ends, np.diff(ends, prepend=0))]
 
 
 def gauss(n=11, sigma=1):

@@ -14,12 +14,10 @@ exist there).
 import os
 import sys
 import types
-from pathlib import Path
 
 import numpy as np
 
 REFERENCE_ROOT = os.environ.get("FRITURE_REFERENCE", "/root/reference")
-sys.path.append(str(Path(__file__).resolve().parents[1] / "tests"))      # the recorders' case definitions: tests/*_helpers.py
 
 
 def available() -> bool:

@@ -1,4 +1,4 @@
-"""Shared by oracle/golden_scope.py and the scope tests: the fixture's cases (signals regenerated from seeds, never stored;
+"""The oscilloscope's cases and CPU restatement, shared by oracle/golden_scope.py and the scope tests: the fixture's cases (signals regenerated from seeds, never stored;
 chunk schedules; timerange schedules) and a numpy restatement of Scope_Widget.handle_new_data (friture/scope.py:78-135) over
 the zero-padded stream, the form the kernels compute (friture_amd/csrc/scope.hip)."""
 from __future__ import annotations
@@ -7,8 +7,8 @@ import hashlib
 
 import numpy as np
 
-FS = 48000
-CHUNK = 512
+from .cases import CHUNK, FS, chunk_ends  # noqa: F401  (chunk_ends: used by the tests)
+
 NO_TRIGGER = -(1 << 63)
 IRREGULAR_CHUNKS = [512, 0, 7, 1, 10, 513, 2048, 0, 300, 4099, 1, 8192, 65, 11, 9000, 512, 0, 3, 255, 1024, 333, 6000, 2,
                     512, 777, 5000, 64, 128, 3000]
@@ -33,10 +33,6 @@ def trace_length(width, scrolling):
 def scaled_t(width, timerange, length):
     time = (np.arange(length) - width // 2) / float(FS)
     return (time * 1e3 + timerange / 2.) / timerange
-
-
-def chunk_ends(T, chunk=CHUNK):
-    return np.minimum(np.arange(1, -(-T // chunk) + 1, dtype=np.int64) * chunk, T)
 
 
 def tone_noise(T, seed, rows=2):

@@ -1,13 +1,13 @@
-"""Shared by the SpectrumBatch tests: the spectrum widget's body replayed with the oracle (the loop of
+"""Shared by the SpectrumBatch tests and tools/bench_spectrumbatch.py: the spectrum widget's body replayed with the oracle (the loop of
 test_widgets_gpu.test_spectrum_analyzer_stream, over streams, dual channels and ragged chunk ends, every refresh kept), seeded
 inputs, and the check that an oracle result decides its own arg-max indices."""
 from __future__ import annotations
 
 import numpy as np
 
-from oracle import dsp
+from . import dsp
+from .cases import FS, chunk_ends
 
-FS = 48000
 NK = 8192
 
 
@@ -20,10 +20,6 @@ def settings(fft_size, overlap, weighting, response_time):
     curves = dsp.weighting_curves(freq)
     weight = np.zeros(freq.shape) if weighting == 0 else curves[min(weighting, 3) - 1]
     return int(needed), needed, alpha, dsp.smoothing_kernel(alpha, NK), weight, freq
-
-
-def chunk_ends(T, chunk=512):
-    return np.minimum(np.arange(1, -(-T // chunk) + 1, dtype=np.int64) * chunk, T)
 
 
 def replay_schedule(fft_size, overlap, ends, pending=0):

@@ -6,7 +6,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import levels_helpers as H
+from oracle import levels as H
 
 GOLDEN = Path(__file__).resolve().parent / "golden" / "levels.npz"
 

@@ -1,12 +1,13 @@
 """The plot curves without a GPU: host edges, labels and baselines of friture_amd.plotcurves and the numpy restatement of
-tests/plotcurves_helpers.py against tests/golden/plotcurves.npz (recorded from the reference SpectrumPlotWidget and HistPlot),
+oracle/plotcurves.py against tests/golden/plotcurves.npz (recorded from the reference SpectrumPlotWidget and HistPlot),
 bit for bit; the decay step the kernel carries; the C ABI entry points."""
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-import plotcurves_helpers as H
+from oracle import plotcurves as H
+from plotcurves_helpers import check_case
 
 GOLDEN = Path(__file__).resolve().parent / "golden" / "plotcurves.npz"
 ROOT = Path(__file__).resolve().parents[1]
@@ -43,14 +44,14 @@ def _numpy_widget(cls):
 def test_spectrum_host_parts_and_restatement_match_reference(g, name):
     from friture_amd.plotcurves import SpectrumPlot
     with np.errstate(invalid="ignore"):
-        H.check_case(g, name, _numpy_widget(SpectrumPlot)())
+        check_case(g, name, _numpy_widget(SpectrumPlot)())
 
 
 @pytest.mark.parametrize("name", H.HIST_CASES)
 def test_histplot_host_parts_and_restatement_match_reference(g, name):
     from friture_amd.plotcurves import HistPlot
     with np.errstate(invalid="ignore"):
-        H.check_case(g, name, _numpy_widget(HistPlot)())
+        check_case(g, name, _numpy_widget(HistPlot)())
 
 
 def test_cases_cover_the_issue(g):

@@ -5,7 +5,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import plotcurves_helpers as H
+from oracle import plotcurves as H
+from plotcurves_helpers import check_case
 
 pytestmark = pytest.mark.gpu
 GOLDEN = Path(__file__).resolve().parent / "golden" / "plotcurves.npz"
@@ -36,13 +37,13 @@ def _rows(rng, S, R, B, holes=True):
 @pytest.mark.parametrize("name", H.SPECTRUM_CASES)
 def test_spectrum_plot_matches_reference(g, name):
     from friture_amd.plotcurves import SpectrumPlot
-    H.check_case(g, name, SpectrumPlot())
+    check_case(g, name, SpectrumPlot())
 
 
 @pytest.mark.parametrize("name", H.HIST_CASES)
 def test_histplot_matches_reference(g, name):
     from friture_amd.plotcurves import HistPlot
-    H.check_case(g, name, HistPlot())
+    check_case(g, name, HistPlot())
 
 
 def test_batch_equals_widget():

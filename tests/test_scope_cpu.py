@@ -1,11 +1,11 @@
 """The oscilloscope without a GPU: width and region arithmetic, chunk schedules, the time axis, and the numpy restatement of
-tests/scope_helpers.py against tests/golden/scope.npz (recorded from the reference Scope_Widget)."""
+oracle/scope.py against tests/golden/scope.npz (recorded from the reference Scope_Widget)."""
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-import scope_helpers as H
+from oracle import scope as H
 
 GOLDEN = Path(__file__).resolve().parent / "golden" / "scope.npz"
 

@@ -5,7 +5,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import scope_helpers as H
+from oracle import scope as H
 
 pytestmark = pytest.mark.gpu
 GOLDEN = Path(__file__).resolve().parent / "golden" / "scope.npz"

@@ -3,7 +3,7 @@ properties the GPU tests lean on, and the new entry point in the header, the cty
 import numpy as np
 import pytest
 
-import spectrumbatch_helpers as H
+from oracle import spectrumbatch as H
 from friture_amd.spectrum import SpectrumBatch, SpectrumState
 
 

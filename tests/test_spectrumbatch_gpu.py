@@ -1,15 +1,15 @@
 """SpectrumBatch on the GPU: frt_spectrum_batch alone on given PSD frames, the whole chain from samples against the oracle
 replay and against the per-chunk SpectrumAnalyzerStream, split and slab invariance bit for bit, the hand-over to CurveBatch,
 silence, argument errors.  Tolerances are those of tests/test_widgets_gpu.py for the same stages (smoothed 1e-13 relative, dB
-1e-9 on given PSD frames and 1e-8 from samples); index equality is asserted only where spectrumbatch_helpers.assert_decisive
+1e-9 on given PSD frames and 1e-8 from samples); index equality is asserted only where oracle.spectrumbatch.assert_decisive
 holds on the oracle's own values."""
 import ctypes
 
 import numpy as np
 import pytest
 
-import plotcurves_helpers as PH
-import spectrumbatch_helpers as H
+from oracle import plotcurves as PH
+from oracle import spectrumbatch as H
 from conftest import rel_max
 from oracle import dsp
 

@@ -7,12 +7,13 @@ and writes it to --out when given.  Per-kernel times come from a separate `rocpr
 from __future__ import annotations
 
 import argparse
-import json
 import sys
 import time
 from pathlib import Path
 
 import numpy as np
+
+from benchutil import HBM_PEAK, emit, time_call
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
@@ -50,22 +51,13 @@ def main():
         T = 1 << 22
         x = (0.1 * torch.randn(C, T, device="cuda", dtype=torch.float64)).to(dt)
         lb = LevelsBatch(C, 20, 512)
-        lb.run(x)
+        m, lo = lb.run(x)
         torch.cuda.synchronize()
-        ts = []
-        for _ in range(a.reps):
-            lb.reset()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            m, lo = lb.run(x)
-            e1.record()
-            torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1) * 1e-3)
+        med, tmin, tmax = time_call(lambda: lb.run(x), a.reps, before_each=lb.reset)
         nbytes = x.numel() * x.element_size() + m.numel() * 8 + lo.numel() * 8
-        med = float(np.median(ts))
         res["batch"].append({"channels": C, "samples": T, "dtype": str(dt).split(".")[-1], "chunk": 512, "rt": 20,
-                             "median_ms": med * 1e3, "min_ms": min(ts) * 1e3, "max_ms": max(ts) * 1e3, "bytes": nbytes,
-                             "GBps": nbytes / med / 1e9, "hbm_share": nbytes / med / 8e12})
+                             "median_ms": med * 1e3, "min_ms": tmin * 1e3, "max_ms": tmax * 1e3, "bytes": nbytes,
+                             "GBps": nbytes / med / 1e9, "hbm_share": nbytes / med / HBM_PEAK})
     if not a.batch_only:
         rng = np.random.default_rng(0)
         chunks = [0.1 * rng.standard_normal((2, 512)) for _ in range(400)]
@@ -82,11 +74,7 @@ def main():
             return float(np.median(ts)) * 1e6
         res["interactive_us_p50"] = {"Levels_2ch": p50(lv.handle_new_data), "LongLevels": p50(ll.handle_new_data),
                                      "numpy_meter_chain_2ch": p50(numpy_chain(lv.kernel, lv.alpha, lv.alpha2))}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.out).write_text(line + "\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -4,23 +4,21 @@ Batch: (a) 64 streams x 64 refreshes x 8193 bins float64, every output; (b) the 
 refreshes x 27 bands float32, the layout of FirBank.energies(..., as_db=True), every output.  Device events around the call after a
 warm-up, repeated.  Bytes are what the algorithm must move: the input once, the state in and out, the outputs, as a share of the
 8 TB/s HBM peak.  Interactive: p50 of one SpectrumPlot.setdata at 8193 bins and one HistPlot.setdata at 27 bands, against the
-numpy body of tests/plotcurves_helpers.NumpyCurves plus the edges the widgets recompute every refresh.  Prints one JSON line and
+numpy body of oracle.plotcurves.NumpyCurves plus the edges the widgets recompute every refresh.  Prints one JSON line and
 writes it to --out when given.  Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run."""
 from __future__ import annotations
 
 import argparse
-import json
 import sys
 import time
 from pathlib import Path
 
 import numpy as np
 
+from benchutil import HBM_PEAK, emit, time_call
+
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "tests"))
-
-HBM_PEAK = 8e12
 
 
 def main():
@@ -42,24 +40,16 @@ def main():
         cb = CurveBatch(-100., 0.)
         r = cb.run(y, keep=keep)
         torch.cuda.synchronize()
-        ts = []
-        for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            r = cb.run(y, keep=keep)
-            e1.record()
-            torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1) * 1e-3)
+        med, tmin, tmax = time_call(lambda: cb.run(y, keep=keep), a.reps)
         nbytes = y.numel() * y.element_size() + 2 * r.state.numel() * 8 + sum(o.numel() * 8 for o in r[:4])
-        med = float(np.median(ts))
         res["batch"].append({"workload": label, "streams": S, "refreshes": R, "bins": B, "dtype": str(dt).split(".")[-1],
-                             "keep": keep, "median_ms": med * 1e3, "min_ms": min(ts) * 1e3, "max_ms": max(ts) * 1e3,
+                             "keep": keep, "median_ms": med * 1e3, "min_ms": tmin * 1e3, "max_ms": tmax * 1e3,
                              "bytes": nbytes, "GBps": nbytes / med / 1e9, "hbm_share": nbytes / med / HBM_PEAK,
                              "ns_per_refresh_per_lane_walk": med / R * 1e9})
         del y, r
         torch.cuda.empty_cache()
     if not a.batch_only:
-        import plotcurves_helpers as H
+        from oracle import plotcurves as H
         from friture_amd.plotting import frequency_scales as fs
         rng = np.random.default_rng(0)
 
@@ -101,11 +91,7 @@ def main():
             "numpy_spectrum_body_8193": p50(numpy_spectrum, spec_rows),
             "HistPlot_27": p50(lambda y: hp.setdata(fl, fh, fc, y), hist_rows),
             "numpy_hist_body_27": p50(numpy_hist, hist_rows)}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.out).write_text(line + "\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

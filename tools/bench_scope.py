@@ -9,17 +9,16 @@ one JSON line and writes it to --out when given.  Per-kernel times come from a s
 from __future__ import annotations
 
 import argparse
-import json
 import sys
 import time
 from pathlib import Path
 
 import numpy as np
 
+from benchutil import HBM_PEAK, emit, time_call
+
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-
-HBM_PEAK = 8e12
 
 
 def numpy_body(ring, timerange=50):
@@ -71,22 +70,14 @@ def main():
         sb = ScopeBatch(tr)
         r = sb.run(x, chunk=chunk, traces=traces)
         torch.cuda.synchronize()
-        ts = []
-        for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            r = sb.run(x, chunk=chunk, traces=traces)
-            e1.record()
-            torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1) * 1e-3)
+        med, tmin, tmax = time_call(lambda: sb.run(x, chunk=chunk, traces=traces), a.reps)
         K = r.starts.shape[1]
         rows_read = 2 if traces else 1
         nbytes = S * rows_read * T * x.element_size() + r.starts.numel() * 8 + (r.traces.numel() * 8 if traces else 0)
-        med = float(np.median(ts))
         res["batch"].append({"streams": S, "rows": 2, "samples": T, "dtype": "float32", "chunk": chunk, "timerange_ms": tr,
                              "width": sb.width, "refreshes": K, "traces": traces or "none",
                              "triggered_share": float(r.triggered.float().mean().item()),
-                             "median_ms": med * 1e3, "min_ms": min(ts) * 1e3, "max_ms": max(ts) * 1e3, "bytes": nbytes,
+                             "median_ms": med * 1e3, "min_ms": tmin * 1e3, "max_ms": tmax * 1e3, "bytes": nbytes,
                              "GBps": nbytes / med / 1e9, "hbm_share": nbytes / med / HBM_PEAK,
                              "ns_per_refresh": med / (S * K) * 1e9})
         del x, r
@@ -120,11 +111,7 @@ def main():
                                      "numpy_widget_body_2ch": p50(ref, numpy_body(ref))}
         # the numpy body per refresh, times the refreshes of the 64-stream batch: what the restatement would take
         res["numpy_batch_estimate_ms_64x2^22_w2400"] = res["interactive_us_p50"]["numpy_widget_body_2ch"] * 64 * (T // chunk) * 1e-3
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.out).write_text(line + "\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@ Shapes: (a) 64 streams x 2^22 float32 samples at the defaults (fft_size 8192, 75
 tensor after a warm-up, median / min / max of --reps); the per-refresh route on the same data — StftEngine(..., 64).psd once plus
 one frt_spectrum_post per refresh on device buffers, what SpectrumAnalyzerStream._post_dev does — timed on ONE stream and the
 first --route-refreshes refreshes with a host clock (every call ends in a synchronisation) and scaled linearly to all refreshes
-and streams; the numpy oracle replay (tests/spectrumbatch_helpers.replay) on one stream and its first --oracle-refreshes
+and streams; the numpy oracle replay (oracle.spectrumbatch.replay) on one stream and its first --oracle-refreshes
 refreshes, scaled the same way.  Bytes are what the algorithm must move: samples read, float64 PSD written and read, dB written,
 as a share of the 8 TB/s HBM peak.  Prints one JSON line and writes it to --out when given.  The split between the STFT launch
 and the new kernels comes from a separate `rocprofv3 --kernel-trace --stats` run of this tool with --batch-only."""
@@ -13,18 +13,17 @@ from __future__ import annotations
 
 import argparse
 import ctypes
-import json
 import sys
 import time
 from pathlib import Path
 
 import numpy as np
 
+from benchutil import HBM_PEAK, emit, time_call
+
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "tests"))
 
-HBM_PEAK = 8e12
 SHAPES = [("a", 64, 1 << 22, 8192), ("b", 1, 1 << 22, 8192), ("c", 64, 1 << 20, 1024)]
 
 
@@ -86,26 +85,17 @@ def main():
         R, B = r.db.shape[1], r.db.shape[2]
         F = int(sb.schedule(T)[0][-1])
         del r
-        ts = []
-        for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            r = sb.run(x)
-            e1.record()
-            torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1) * 1e-3)
-            del r
-        med = float(np.median(ts))
+        med, tmin, tmax = time_call(lambda: sb.run(x), a.reps)
         nbytes = S * T * 4 + 2 * S * F * B * 8 + S * R * B * 8
         row = {"shape": label, "streams": S, "samples": T, "fft_size": N, "refreshes": R, "frames": F, "bins": B,
-               "batch_median_ms": med * 1e3, "batch_min_ms": min(ts) * 1e3, "batch_max_ms": max(ts) * 1e3, "reps": a.reps,
+               "batch_median_ms": med * 1e3, "batch_min_ms": tmin * 1e3, "batch_max_ms": tmax * 1e3, "reps": a.reps,
                "algorithmic_bytes": nbytes, "GBps": nbytes / med / 1e9, "hbm_share": nbytes / med / HBM_PEAK}
         if not a.batch_only:
             dt, nr = route_per_refresh(torch, _lib, sb, x[0], a.route_refreshes)
             row["per_refresh_route_ms_scaled"] = dt / nr * R * S * 1e3
             row["per_refresh_route_measured"] = f"1 stream, first {nr} refreshes: {dt * 1e3:.2f} ms, scaled by {R}/{nr} x {S} streams"
             row["batch_beats_route"] = bool(med < dt / nr * R * S)
-            import spectrumbatch_helpers as H
+            from oracle import spectrumbatch as H
             no = min(a.oracle_refreshes, R)
             n_samp = (int(sb.schedule(T)[1][no - 1]) + 1) * 512
             xo = x[0, :n_samp].cpu().numpy().astype(np.float64)[None, None]
@@ -117,11 +107,7 @@ def main():
         res["shapes"].append(row)
         del x
         torch.cuda.empty_cache()
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.out).write_text(line + "\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":
