@@ -1,4 +1,4 @@
-"""What the batch classes (LevelsBatch, ScopeBatch, CurveBatch, SpectrumBatch) share: their input is a float32/float64 numpy
+"""What the batch classes (LevelsBatch, ScopeBatch, CurveBatch, SpectrumBatch, SpectrogramBatch) share: their input is a float32/float64 numpy
 array or CUDA tensor, their results are of the same kind, and a recording is seen in chunks."""
 from __future__ import annotations
 
@@ -8,6 +8,31 @@ import numpy as np
 def chunk_ends(T, chunk=512):
     """The stream ends at which a widget fed `chunk`-sample chunks refreshes (a short last chunk is a short chunk)."""
     return np.minimum(np.arange(1, -(-T // chunk) + 1, dtype=np.int64) * chunk, T)
+
+
+def frame_schedule(n_samples, needed, hop, chunk=512, ends=None, pending=0):
+    """(frame_start [R + 1], refresh_chunk [R]) of a stream of n_samples seen chunk by chunk by a widget that transforms
+    realizable = floor(available / needed) frames per chunk and advances by hop = int(needed) per frame (friture/spectrum.py:
+    133-155, friture/spectrogram.py:131-160); `pending`: samples received and not consumed before the first one.  `ends`: the
+    chunks' end indices, for ragged chunks; default: the ends of `chunk`-sample chunks, a short last chunk is a short chunk."""
+    n_samples = int(n_samples)
+    if ends is None:
+        if chunk < 1:
+            raise ValueError(f"chunk {chunk}")
+        ends = chunk_ends(n_samples, chunk)
+    else:
+        ends = np.asarray(ends, np.int64).reshape(-1)
+        if ends.size and (ends[0] < 0 or ends[-1] > n_samples or np.any(np.diff(ends) < 0)):
+            raise ValueError(f"ends must be sorted and within [0, {n_samples}]")
+    old_index = -int(pending)
+    frame_start, refresh_chunk = [0], []
+    for c, e in enumerate(ends.tolist()):
+        realizable = int(np.floor((e - old_index) / needed))
+        if realizable > 0:
+            frame_start.append(frame_start[-1] + realizable)
+            refresh_chunk.append(c)
+            old_index += realizable * hop
+    return np.array(frame_start, np.int64), np.array(refresh_chunk, np.int64)
 
 
 def ptr(a):

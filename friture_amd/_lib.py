@@ -129,6 +129,8 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "frt_spectrum_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, POINTER(c_int64), c_int64,
                                    c_void_p, c_int, c_double, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "frt_specgram_batch": (c_int, [c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                   c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

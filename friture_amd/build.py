@@ -35,7 +35,7 @@ CXXFLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-W
 # the top and 16 v_accvgpr_read (+ s_nop 8) at the bottom of every trip of 16 MFMAs (profiles/r06_iir_zero_state_pipeline.txt: -3 .. -6 us per call)
 EXTRA_FLAGS = {"iir.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form"], "pipeline.hip": ["-ffp-contract=off"], "pitch.hip": ["-ffp-contract=off"],
                "specgram.hip": ["-ffp-contract=off"], "levels.hip": ["-ffp-contract=off"], "scope.hip": ["-ffp-contract=off"],
-               "curves.hip": ["-ffp-contract=off"], "spectrumbatch.hip": ["-ffp-contract=off"],
+               "curves.hip": ["-ffp-contract=off"], "spectrumbatch.hip": ["-ffp-contract=off"], "specgrambatch.hip": ["-ffp-contract=off"],
                "stft.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"]}
 
 

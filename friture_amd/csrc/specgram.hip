@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "screen_interp.h"
 
 namespace frt {
 
@@ -49,16 +50,8 @@ __global__ void __launch_bounds__(256) ring_relay_kernel(const double* __restric
     new_ring[p + new_len] = v;
 }
 
-// One thread per (pixel column p, screen row h).  norm: [frames][nb] (frame-major, what stft_kernel writes).
-// np.interp with the interval index found on the host (frequency_resampler.py:80; same branches as freq_resample_kernel).
-__device__ __forceinline__ double freq_interp(const double* __restrict__ col, int nb, int j, double dx, double den) {
-    if (j < 0) return col[0];
-    if (j >= nb - 1) return col[nb - 1];
-    const double f0 = col[j];
-    if (dx == 0.0) return f0;
-    const double slope = (col[j + 1] - f0) / den;
-    return slope * dx + f0;
-}
+// One thread per (pixel column p, screen row h).  norm: [frames][nb] (frame-major, what stft_kernel writes); freq_interp
+// and interval_search: screen_interp.h.
 
 // A chunk rarely yields more than a handful of pixel columns: their source frame and weight then travel in the kernel
 // arguments (no separate upload in front of the launch).
@@ -91,27 +84,6 @@ __global__ void __launch_bounds__(64) screen_columns_kernel(const double* __rest
     double v = cur * (1.0 - w) + prev * w;               // linear_interp.py:57-60
     v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);             // numpy.clip (NaN falls through to the cast like numpy's)
     pixels[(size_t)(flip ? height - 1 - h : h) * pixel_stride + p] = lut[(int)(v * 255.0)];
-}
-
-// numpy.interp's interval search for the screen rows (largest j with freq[j] <= x; -1 / nb outside the table)
-static void interval_search(const double* freq, int nb, const double* targets, int height, int* j, double* dx, double* den) {
-    for (int r = 0; r < height; ++r) {
-        const double x = targets[r];
-        dx[r] = 0.0;
-        den[r] = 1.0;
-        if (!(x >= freq[0])) { j[r] = -1; continue; }
-        if (x > freq[nb - 1]) { j[r] = nb; continue; }
-        int lo = 0, hi = nb;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) / 2;
-            if (freq[mid] <= x) lo = mid; else hi = mid;
-        }
-        j[r] = lo;
-        if (lo < nb - 1) {
-            dx[r] = x - freq[lo];
-            den[r] = freq[lo + 1] - freq[lo];
-        }
-    }
 }
 
 }  // namespace frt

@@ -16,6 +16,30 @@ from .. import _lib
 from .scipy_resample import resample
 
 
+def advance_indices(orig_index, resampled_index, ratio, n_cols):
+    """The scalar index bookkeeping of a push of n_cols columns, as in the reference (online_linear_2D_resampler.py:61-97), as a
+    pure function: returns (columns the reference allocates, source column per emitted pixel column, its weight, the new
+    orig_index, the new resampled_index).  Same float64 operations in the same order as the reference's numpy expressions
+    (resampled_index + ratio * k, k = 1..n), on Python floats: a chunk advances by one or two columns, where array temporaries
+    cost more than the arithmetic."""
+    ceil = math.ceil
+    total = int(ceil((orig_index + n_cols - (resampled_index + ratio)) / ratio))
+    src, weights = [], []
+    orig, res = orig_index, resampled_index
+    for j in range(n_cols):
+        orig += 1.
+        n = int(ceil((orig - (res + ratio)) / ratio))
+        if n <= 0:
+            continue
+        last = res
+        for k in range(1, n + 1):
+            last = res + ratio * float(k)
+            weights.append(orig - last)
+            src.append(j)
+        res = last
+    return total, src, weights, orig, res
+
+
 class Online_Linear_2D_resampler:
     def __init__(self, interp_factor_L=1, decim_factor_M=1, height=1):
         self._lib = _lib.init()
@@ -48,27 +72,9 @@ class Online_Linear_2D_resampler:
         return int(np.ceil((self.orig_index + m - (self.resampled_index + self.resampling_ratio)) / self.resampling_ratio))
 
     def advance(self, n_cols):
-        """The scalar index bookkeeping of a push of n_cols columns, as in the reference (online_linear_2D_resampler.py:61-97):
-        returns (columns the reference allocates, source column per emitted pixel column, its weight).  Same float64
-        operations in the same order as the reference's numpy expressions (resampled_index + ratio * k, k = 1..n), on
-        Python floats: a chunk advances by one or two columns, where array temporaries cost more than the arithmetic."""
-        ceil = math.ceil
-        ratio = self.resampling_ratio
-        total = int(ceil((self.orig_index + n_cols - (self.resampled_index + ratio)) / ratio))
-        src, weights = [], []
-        orig, res = self.orig_index, self.resampled_index
-        for j in range(n_cols):
-            orig += 1.
-            n = int(ceil((orig - (res + ratio)) / ratio))
-            if n <= 0:
-                continue
-            last = res
-            for k in range(1, n + 1):
-                last = res + ratio * float(k)
-                weights.append(orig - last)
-                src.append(j)
-            res = last
-        self.orig_index, self.resampled_index = orig, res
+        """The scalar index bookkeeping of a push of n_cols columns (advance_indices), applied to this object."""
+        total, src, weights, self.orig_index, self.resampled_index = advance_indices(self.orig_index, self.resampled_index,
+                                                                                    self.resampling_ratio, n_cols)
         return total, np.array(src, np.int32), np.array(weights, np.float64)
 
     def push(self, data):

@@ -1,19 +1,24 @@
 """The spectrogram widget's processing chain (friture/spectrogram.py:131-177) without its Qt shell:
 ring buffer, batched float64 STFT of every realizable frame, dB + weighting + normalisation, then the
-Transform_Pipeline (frequency resampler -> online time resampler -> colour transform) to pixels."""
+Transform_Pipeline (frequency resampler -> online time resampler -> colour transform) to pixels.
+
+`SpectrogramBatch` runs the same chain over whole recordings, many streams at a time, in device calls
+(frt_specgram_batch, specgrambatch.hip)."""
 from __future__ import annotations
 
 from fractions import Fraction
+from typing import NamedTuple
 
 import numpy as np
 
+from ._batchio import frame_schedule
 from .audioproc import audioproc
 from .constants import SAMPLING_RATE
 from .plotting import frequency_scales as fscales
 from .ringbuffer import RingBuffer
 from .signal.color_tranform import Color_Transform
 from .signal.frequency_resampler import Frequency_Resampler
-from .signal.online_linear_2D_resampler import Online_Linear_2D_resampler
+from .signal.online_linear_2D_resampler import Online_Linear_2D_resampler, advance_indices
 from .signal.transform_pipeline import Transform_Pipeline
 from .stft import StftEngine
 
@@ -191,3 +196,221 @@ class SpectrogramStream:
         if n_frames.value == 0:
             return None
         return out[:, :n_cols.value]
+
+
+# ---- the same chain over whole recordings ---------------------------------------------------------------------------------
+
+class SpectrogramState(NamedTuple):
+    """What a spectrogram widget carries between two calls: the samples it still needs, how many of them it has received but
+    not consumed, and the time resampler's carried column and indices."""
+    tail: object            # [S, fft_size + pending] float64: samples [old_index - fft_size, offset), zeros before the start
+    pending: int            # offset - old_index
+    old_column: object      # [S, screen_height] float64: the frequency-resampled last frame
+    orig_index: float       # Online_Linear_2D_resampler.orig_index
+    resampled_index: float  # Online_Linear_2D_resampler.resampled_index
+
+
+class ColumnTable(NamedTuple):
+    """Which frame feeds which pixel column (host arrays)."""
+    src: object             # [P] int64: the source frame (index into the schedule's frames); the frame before it is the other end
+    a: object               # [P] float64: pixel = frame[src] (1 - a) + frame[src - 1] a
+    filler: object          # [P] bool: a column the reference allocated and never wrote (lut[0])
+    column_refresh: object  # [P] int64: the refresh that emitted the column
+    orig_index: float       # the resampler's indices after the last refresh
+    resampled_index: float
+
+
+class SpectrogramResult(NamedTuple):
+    pixels: object          # [S, screen_height, P'] uint32, row 0 = highest frequency ([screen_height, P'] for one stream given without its axis)
+    column_refresh: object  # [P'] int64 (host): the refresh that emitted each column
+    refresh_chunk: object   # [R] int64 (host): the chunk that caused each refresh
+    state: SpectrogramState
+
+
+class SpectrogramBatch:
+    """S streams of a whole recording through the spectrogram widget's chain in device calls, as widgets fed chunk by chunk would
+    have painted it: per time slab one float64 STFT with the normalising epilogue over all streams, then frt_specgram_batch
+    (specgrambatch.hip: np.interp onto the screen rows, the time resampler's lerp, clip + LUT, flipped rows).  Fixed settings, no
+    pause, no resize.  run(x, chunk=512 | ends=..., state=None, keep="all" | "screen") takes [S, T] (the stream axis may be left
+    out), float32 or float64, numpy array or CUDA tensor; pixels are numpy for numpy input and a CUDA tensor for CUDA input.
+    keep="screen" produces only the last min(P, screen_width) columns (what the rolling canvas shows at the end) and transforms
+    only the frames they need.  The normalised frames between the two stages live in at most `scratch_bytes` of device memory (or
+    one refresh, if that is larger): longer recordings go through in time slabs, with the same bits whatever the slab size."""
+
+    def __init__(self, fft_size=DEFAULT_FFT_SIZE, overlap=Fraction(3, 4), spec_min=-140., spec_max=0., weighting=0,
+                 scale=fscales.Mel, minfreq=20., maxfreq=20000., screen_width=800, screen_height=400, timerange_s=DEFAULT_TIMERANGE):
+        from . import palette, tables
+        self.fft_size = int(fft_size)
+        self.overlap_frac = Fraction(overlap)
+        self.spec_min, self.spec_max, self.weighting = spec_min, spec_max, weighting
+        self.scale, self.minfreq, self.maxfreq = scale, minfreq, maxfreq
+        self.screen_width, self.screen_height, self.timerange_s = int(screen_width), int(screen_height), timerange_s
+        self.needed = self.fft_size * (1. - float(self.overlap_frac))       # a float, as in the widget
+        self.hop = int(self.needed)
+        if self.fft_size < 4 or self.fft_size % 2 or self.hop < 1:
+            raise ValueError(f"fft_size {fft_size} with overlap {overlap}: no frame advance")
+        if self.screen_height < 1 or int(timerange_s * 1000) < 1:
+            raise ValueError(f"screen height {screen_height}, time range {timerange_s} s")
+        self.freq = tables.rfft_frequencies(self.fft_size)
+        self.n_bins = len(self.freq)
+        A, B, C = tables.weighting_db(self.freq, floor=1e-50)
+        self.w = {0: np.zeros(A.shape), 1: A, 2: B}.get(weighting, C)
+        self.targets = np.ascontiguousarray(scale.inverse(np.linspace(scale.transform(minfreq), scale.transform(maxfreq),
+                                                                      self.screen_height)), np.float64)
+        self.lut = np.ascontiguousarray(palette.cmr_lut(), np.uint32)
+        sfft_rate_frac = Fraction(SAMPLING_RATE, self.fft_size) / (Fraction(1) - self.overlap_frac) / 1000
+        screen_rate_frac = Fraction(max(self.screen_width, 1), int(timerange_s * 1000))
+        self.ratio = float(sfft_rate_frac) / float(screen_rate_frac)        # set_ratio: float(L) / M (online_linear_2D_resampler.py:38)
+        self._engines = {}
+
+    # ---- host only ------------------------------------------------------------------------------------------------------------
+    def schedule(self, n_samples, chunk=512, ends=None, state=None):
+        """(frame_start [R + 1], refresh_chunk [R]): SpectrumBatch.schedule's, the two widgets keep the same bookkeeping.  Refresh r
+        consumes the frames frame_start[r] .. frame_start[r + 1] - 1; frame j is the fft_size samples ending at j * hop - pending."""
+        return frame_schedule(n_samples, self.needed, self.hop, chunk, ends, 0 if state is None else state.pending)
+
+    def columns(self, n_samples, chunk=512, ends=None, state=None):
+        """The ColumnTable of the recording: the time resampler's scalar recurrence replayed refresh by refresh (the widget pushes the
+        frames of one refresh at once).  The reference sizes a push's block from processable(m) and fills it frame by frame; in
+        float arithmetic the two counts can differ by one: a column allocated and not written is a `filler`, a refresh that would
+        write more columns than were allocated raises ValueError (the reference raises there too)."""
+        frame_start, _ = self.schedule(n_samples, chunk, ends, state)
+        orig, res = (0., 0.) if state is None else (float(state.orig_index), float(state.resampled_index))
+        src, a, filler, col_refresh = [], [], [], []
+        for r in range(len(frame_start) - 1):
+            f0, m = int(frame_start[r]), int(frame_start[r + 1] - frame_start[r])
+            total, s, w, orig, res = advance_indices(orig, res, self.ratio, m)
+            if len(s) > total:
+                raise ValueError(f"refresh {r}: the time resampler emits {len(s)} columns for {m} frames where the reference "
+                                 f"allocates {total}")
+            src += [f0 + j for j in s] + [f0 + m - 1] * (total - len(s))
+            a += w + [0.] * (total - len(s))
+            filler += [False] * len(s) + [True] * (total - len(s))
+            col_refresh += [r] * total
+        return ColumnTable(np.array(src, np.int64), np.array(a, np.float64), np.array(filler, bool), np.array(col_refresh, np.int64),
+                           orig, res)
+
+    # ---- device ---------------------------------------------------------------------------------------------------------------
+    def _check_input(self, x, state):
+        is_np = isinstance(x, np.ndarray)
+        if not is_np and not (type(x).__module__.startswith("torch") and x.is_cuda):
+            raise TypeError("SpectrogramBatch.run takes a numpy array or a CUDA tensor")
+        if x.ndim not in (1, 2):
+            raise ValueError(f"expected [S, T] (the stream axis may be left out), got {tuple(x.shape)}")
+        if str(x.dtype).split(".")[-1] not in ("float32", "float64"):
+            raise TypeError(f"samples must be float32 or float64, got {x.dtype}")
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        S, T = x.shape
+        if S < 1:
+            raise ValueError("no stream")
+        pending = 0
+        if state is not None:
+            pending = int(state.pending)
+            want_tail, want_old = (S, self.fft_size + pending), (S, self.screen_height)
+            if pending < 0 or tuple(state.tail.shape) != want_tail or tuple(state.old_column.shape) != want_old:
+                raise ValueError(f"state of another shape: tail {tuple(state.tail.shape)} (want {want_tail}), old_column "
+                                 f"{tuple(state.old_column.shape)} (want {want_old}), pending {pending}")
+        return x, is_np, squeeze, S, T, pending
+
+    def run(self, x, chunk=512, ends=None, state=None, keep="all", scratch_bytes=1 << 30):
+        if keep not in ("all", "screen"):
+            raise ValueError(f"keep={keep!r} ('all' or 'screen')")
+        x, is_np, squeeze, S, T, pending = self._check_input(x, state)
+        frame_start, refresh_chunk = self.schedule(T, chunk, ends, state)
+        table = self.columns(T, chunk, ends, state)                 # raises before anything is enqueued
+        if ends is not None:                                        # the widgets were pushed ends[-1] samples
+            T = int(np.asarray(ends).reshape(-1)[-1]) if np.size(ends) else 0
+        import ctypes
+
+        import torch
+
+        from . import _lib
+        lib = _lib.init()
+        dev = torch.device("cuda", torch.cuda.current_device()) if is_np else x.device
+        B, N, hop, H = self.n_bins, self.fft_size, self.hop, self.screen_height
+        R, F, L, P = len(refresh_chunk), int(frame_start[-1]), N + pending, len(table.src)
+        c_lo = 0 if keep == "all" else max(0, P - self.screen_width)                 # the first column produced
+        f_lo = 0 if keep == "all" else (max(0, int(table.src[c_lo]) - 1) if c_lo < P else max(0, F - 1))   # the first frame transformed
+        Po = P - c_lo
+        col_start = np.searchsorted(table.column_refresh, np.arange(R + 1))          # the columns of each refresh
+        src = np.where(table.filler, -1, table.src)
+        f64, vp = torch.float64, ctypes.c_void_p
+        # frt_specgram_batch launches on the null stream (friture_hip.h): everything here is enqueued there, after whatever the
+        # caller's stream still has to do to x
+        mine, null = torch.cuda.current_stream(dev), torch.cuda.default_stream(dev)
+        if mine != null:
+            mine.synchronize()
+        with torch.cuda.device(dev), torch.cuda.stream(null):
+            xd = torch.from_numpy(np.ascontiguousarray(x)).to(dev) if is_np else x
+            if xd.stride(1) != 1:
+                xd = xd.contiguous()
+            if state is None:
+                tail = torch.zeros((S, L), dtype=f64, device=dev)
+                old = torch.zeros((S, H), dtype=f64, device=dev)
+            else:                                                    # copies: the caller's state is not modified
+                tail = torch.as_tensor(state.tail).to(device=dev, dtype=f64).reshape(S, L).contiguous()
+                old = torch.as_tensor(state.old_column).to(device=dev, dtype=f64).reshape(S, H).clone()
+
+            def window(a, b):
+                """Samples [a, b) of tail || x per stream as float64 (float32 widens exactly), unit stride along time."""
+                if a >= L and xd.dtype == f64:
+                    return xd[:, a - L:b - L]
+                out = torch.empty((S, b - a), dtype=f64, device=dev)
+                if a < L:
+                    out[:, :min(b, L) - a] = tail[:, a:min(b, L)]
+                if b > L:
+                    out[:, max(a, L) - a:] = xd[:, max(a, L) - L:b - L]
+                return out
+
+            pixels = torch.empty((S, H, Po), dtype=torch.int32, device=dev)          # uint32 words (torch has no uint32 arithmetic)
+            if R:
+                eng = self._engine(S)
+                _lib.check(lib.frt_stft_set_stream(eng._h, None))
+                # time slabs: whole refreshes, at most fmax normalised frames each (one refresh if it alone has more)
+                fmax = max(1, int(scratch_bytes) // (S * B * 8))
+                slabs, r0 = [], 0
+                while r0 < R:
+                    r1 = max(r0 + 1, int(np.searchsorted(frame_start, frame_start[r0] + fmax, "right")) - 1)
+                    if frame_start[r1] > f_lo:                       # keep="screen": the slabs before the first needed frame drop out
+                        slabs.append((r0, r1))
+                    r0 = r1
+                norm = torch.empty(S * B * max(int(frame_start[b] - max(frame_start[a], f_lo)) for a, b in slabs), dtype=f64, device=dev)
+                old_next = torch.empty_like(old)
+                nfo = ctypes.c_int64(0)
+                for r0, r1 in slabs:
+                    fa, fb = max(int(frame_start[r0]), f_lo), int(frame_start[r1])
+                    ca, cb = max(int(col_start[r0]), c_lo), max(int(col_start[r1]), c_lo)
+                    nf, nc = fb - fa, cb - ca
+                    seg = window(fa * hop, (fb - 1) * hop + N)
+                    _lib.check(lib.frt_stft_run(eng._h, _lib.FRT_STFT_NORM, vp(seg.data_ptr()), seg.shape[1], seg.stride(0) if S > 1 else seg.shape[1],
+                                                vp(norm.data_ptr()), ctypes.byref(nfo)))
+                    assert nfo.value == nf
+                    local = np.ascontiguousarray(np.where(src[ca:cb] < 0, -1, src[ca:cb] - fa), np.int32)
+                    weights = np.ascontiguousarray(table.a[ca:cb])
+                    _lib.check(lib.frt_specgram_batch(
+                        vp(norm.data_ptr()), S, nf, B, B, nf * B, self.freq.ctypes.data, self.targets.ctypes.data, H,
+                        local.ctypes.data if nc else None, weights.ctypes.data if nc else None, nc, vp(old.data_ptr()),
+                        vp(old_next.data_ptr()), self.lut.ctypes.data, vp(pixels.data_ptr()) if nc else None, ca - c_lo, Po))
+                    old, old_next = old_next, old
+                del norm
+            new_tail = window(F * hop, L + T).clone()
+            new_state = SpectrogramState(new_tail, L + T - F * hop - N, old, table.orig_index, table.resampled_index)
+            if is_np:
+                pixels = pixels.cpu().numpy().view(np.uint32)
+                new_state = new_state._replace(tail=new_tail.cpu().numpy(), old_column=old.cpu().numpy())
+            else:
+                pixels = pixels.view(torch.uint32) if hasattr(torch, "uint32") else pixels
+        if mine != null:
+            null.synchronize()
+        if squeeze:
+            pixels = pixels[0]
+        return SpectrogramResult(pixels, table.column_refresh[c_lo:], refresh_chunk, new_state)
+
+    def _engine(self, streams):
+        if streams not in self._engines:
+            eng = StftEngine(self.fft_size, self.hop, streams, 64)
+            eng.set_epilogue(self.w, self.spec_min, self.spec_max, None)
+            self._engines[streams] = eng
+        return self._engines[streams]

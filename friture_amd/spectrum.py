@@ -17,7 +17,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _lib, tables
-from ._batchio import chunk_ends
+from ._batchio import frame_schedule
 from .audioproc import audioproc
 from .constants import SAMPLING_RATE
 from .ringbuffer import RingBuffer
@@ -257,24 +257,7 @@ class SpectrumBatch:
         for ragged chunks; default: the ends of `chunk`-sample chunks, a short last chunk is a short chunk).  Refresh r consumes
         the frames frame_start[r] .. frame_start[r + 1] - 1; frame j is the fft_size samples ending at j * hop - pending, zeros
         before the stream's start, so a fresh widget's frame 0 is all zeros."""
-        n_samples = int(n_samples)
-        if ends is None:
-            if chunk < 1:
-                raise ValueError(f"chunk {chunk}")
-            ends = chunk_ends(n_samples, chunk)
-        else:
-            ends = np.asarray(ends, np.int64).reshape(-1)
-            if ends.size and (ends[0] < 0 or ends[-1] > n_samples or np.any(np.diff(ends) < 0)):
-                raise ValueError(f"ends must be sorted and within [0, {n_samples}]")
-        old_index = -(0 if state is None else int(state.pending))
-        frame_start, refresh_chunk = [0], []
-        for c, e in enumerate(ends.tolist()):
-            realizable = int(np.floor((e - old_index) / self.needed))
-            if realizable > 0:
-                frame_start.append(frame_start[-1] + realizable)
-                refresh_chunk.append(c)
-                old_index += realizable * self.hop
-        return np.array(frame_start, np.int64), np.array(refresh_chunk, np.int64)
+        return frame_schedule(n_samples, self.needed, self.hop, chunk, ends, 0 if state is None else state.pending)
 
     # ---- device ---------------------------------------------------------------------------------------------------------------
     def _check_input(self, x, state):

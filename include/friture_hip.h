@@ -487,6 +487,29 @@ int frt_spectrum_batch(const void* psd, int dtype, int streams, int rows, int64_
                        const double* weight_db, double* state, int keep_last, double* db_out, int64_t ld_db_stream,
                        int* peak_index_out, int* pitch_index_out);
 
+/* ---- P3: the spectrogram widget's screen stages over whole recordings (Spectrogram_Widget.handle_new_data,
+ * friture/spectrogram.py:161-173) ----
+ * One time slab of S streams behind frt_stft_run(FRT_STFT_NORM): per output column c with source frame f = src[c] and weight a[c]
+ *   cur, prev = np.interp(targets, freq, frame f), np.interp(targets, freq, frame f - 1)   (friture/signal/frequency_resampler.py:67-83;
+ *     frame -1 is old_in, the column the time resampler carried into the slab)
+ *   v = cur (1 - a) + prev a                                  (friture/signal/online_linear_2D_resampler.py:61-97, linear_interp.py:57-60)
+ *   pixel = lut256[int(clip(v, 0, 1) * 255)]                  (friture/signal/color_tranform.py:48-51)
+ * written with the frequency axis flipped (friture/spectrogram_image.py:82-92: row 0 = highest frequency).  src[c] < 0 marks a
+ * column the resampler allocated and never wrote (online_linear_2D_resampler.py:66-68): lut256[0].  The operations and their
+ * order are those of frt_screen_columns and frt_specgram_push, so the pixels are theirs bit for bit; the scalar recurrence that
+ * yields (src, a) stays with the caller.  Every frame is frequency-resampled once, whatever the number of columns that read it,
+ * and frames no column reads are not touched.
+ * norm: norm[s * ld_stream + f * ld_frame + b], n_frames >= 1 frames of nb bins, host or device.  freq [nb], targets [height],
+ * lut256 [256], src, a [n_cols]: HOST tables; the source frames ascend.  old_in, old_out: [streams][height], host or device,
+ * distinct buffers; old_out receives the frequency-resampled last frame of the slab.  pixels: pixels[s * height * ld_pixel + row *
+ * ld_pixel + col_offset + c], so that the slabs of a recording fill one image; a host block is written whole (col_offset 0,
+ * ld_pixel = n_cols).  n_cols = 0 only carries the column.  Any height (screen rows are processed in blocks).  Launched on the
+ * null stream (STREAM ORDER as for frt_spectrum_post); one synchronisation at the end. */
+int frt_specgram_batch(const double* norm, int streams, int64_t n_frames, int nb, int64_t ld_frame, int64_t ld_stream,
+                       const double* freq, const double* targets, int height, const int* src, const double* a, int64_t n_cols,
+                       const double* old_in, double* old_out, const uint32_t* lut256, uint32_t* pixels, int64_t col_offset,
+                       int64_t ld_pixel);
+
 #ifdef __cplusplus
 }
 #endif
