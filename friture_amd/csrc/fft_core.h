@@ -13,7 +13,8 @@
 //     consecutive LDS addresses (conflict free), and the first pass takes them straight from the
 //     registers the HBM loads landed in;
 //   * the scatter side of each pass goes through LDS with one pad slot every 8 points, which
-//     makes the stride-8 scatter of the first pass conflict free for ds_write_b64.
+//     makes the stride-8 scatter of the first pass conflict free for ds_write_b64 (LdsPad8); the
+//     one-wavefront M = 512 transform uses an XOR layout that also frees the gathers (LdsXorWave512).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -87,6 +88,27 @@ __device__ __forceinline__ void idft4(cpx<T>& a0, cpx<T>& a1, cpx<T>& a2, cpx<T>
 // One pad slot per 8 points (see header comment).
 __device__ __forceinline__ int lds_pad(int idx) { return idx + (idx >> 3); }
 constexpr int lds_padded_size(int m) { return m + (m >> 3); }
+
+// ---- exchange layouts of fft_pow2_forward ------------------------------------------------------
+// A layout says in which slot of the frame's LDS scratch a point of the exchange lies: at(x), and how many slots a frame needs.
+// LdsPad8, the default: one pad slot per 8 points.  Conflict free for the 16-lane groups a ds_write_b64 is served in, but the
+// 32-lane groups of the ds_read_b64 gather i + 64 j meet every bank twice (i + (i >> 3) wraps three banks): 2-way on every
+// gather (tools/exp/lds_layout_model.py).
+struct LdsPad8 {
+    static constexpr int size(int m) { return lds_padded_size(m); }
+    static __device__ __forceinline__ int at(int x) { return lds_pad(x); }
+};
+
+// LdsXorWave512: the one-wavefront M = 512 transform (two exchanges, 64 lanes).  Point x lies in slot x ^ ((x >> 3) & 15):
+// a bijection on 0..511 (no pad slots) under which both scatters (8 i + q; 64 (i >> 3) + (i & 7) + 8 q) and the gather
+// i + 64 j touch every bank once per lane group, for 8-byte and for 16-byte points (lds_layout_model.py, stft_wave512).
+// A swizzled slot is no longer "lane base + immediate"; the slots depend on the lane and the register slot only, so they are
+// loop invariants of the caller's frame loop.  The accesses are the same struct loads and stores under either layout, so the
+// arithmetic around them compiles to the same instructions (measured: the spectra are bit-identical).
+struct LdsXorWave512 {
+    static constexpr int size(int m) { return m; }
+    static __device__ __forceinline__ int at(int x) { return x ^ ((x >> 3) & 15); }
+};
 
 // Compile-time description of the pass schedule of an M-point transform (M = 2^LOG2M >= 8).
 template <int LOG2M>
@@ -165,8 +187,8 @@ __device__ __forceinline__ void pass_sync() {
 }
 
 // Forward M-point complex FFT of the 8 points v[j] = z[i + j*TPF] held by thread i of a frame.
-// On return v[j] = Z[i + j*TPF].  `buf` is the frame's LDS scratch of lds_padded_size(M) points.
-template <typename T, int LOG2M, bool WAVE_LOCAL, typename TW>
+// On return v[j] = Z[i + j*TPF].  `buf` is the frame's LDS scratch of LAY::size(M) points (default layout: lds_padded_size(M)).
+template <typename T, int LOG2M, bool WAVE_LOCAL, typename LAY = LdsPad8, typename TW>
 __device__ __forceinline__ void fft_pow2_forward(cpx<T> (&v)[8], cpx<T>* buf, int i, const TW& tw) {
     using P = Pow2Plan<LOG2M>;
     constexpr int TPF = P::TPF, M = P::M;
@@ -186,10 +208,10 @@ __device__ __forceinline__ void fft_pow2_forward(cpx<T> (&v)[8], cpx<T>* buf, in
             const int base = (i - k) * 8 + k;
             if (pass > 0) pass_sync<WAVE_LOCAL>();      // everyone has gathered the previous pass
 #pragma unroll
-            for (int q = 0; q < 8; ++q) buf[lds_pad(base + q * p)] = v[q];
+            for (int q = 0; q < 8; ++q) buf[LAY::at(base + q * p)] = v[q];
             pass_sync<WAVE_LOCAL>();
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = buf[lds_pad(i + j * TPF)];
+            for (int j = 0; j < 8; ++j) v[j] = buf[LAY::at(i + j * TPF)];
         }
         p *= 8;
     }

@@ -43,7 +43,7 @@ struct StftArgs {
     int rising;            // max > min: the index grows with the power
     int eps_free;          // P + 1e-30 == P in float32 wherever it matters: the add is skipped
 #ifdef FRT_ABLATE
-    int ablate;            // experiment switches: 1 no stores, 2 no loads, 4 no FFT, 8 no unpack shuffles
+    int ablate;            // experiment switches: 1 no stores, 2 no loads, 4 no FFT, 8 no unpack shuffles, 16 no ninth colour value
 #endif
 };
 
@@ -180,7 +180,14 @@ stft_kernel(const StftArgs a) {
 
     constexpr bool RING = SHIFT < 0;
     static_assert(!RING || (TPF == 64 && sizeof(T) == 4 && sizeof(TIN) == 4), "ring instance: one wavefront per float32 frame");
-    __shared__ C lds[GPB * lds_padded_size(M)];
+    // The exchange layout of the transform.  The register-window instances of N = 1024 (hop N/2 and N/4) swizzle: conflict-free
+    // gathers, fft_core.h.  The instance that reloads the whole frame per hop (SHIFT = 0) sits at the register limit of its
+    // occupancy — the swizzled places would go to scratch, 60 bytes per lane — and the ring instance would drop from four waves per
+    // SIMD to three: both keep the padded layout, like every other size.
+    constexpr bool XOR_LDS = LOG2M == 9 && SHIFT > 0;
+    using Lay = std::conditional_t<XOR_LDS, LdsXorWave512, LdsPad8>;
+    static_assert(!XOR_LDS || TPF == 64, "the XOR layout is the one-wavefront transform's");
+    __shared__ C lds[GPB * Lay::size(M)];
     __shared__ uint32_t lut_lds[256];                // colour words: gathered per bin, keep them on-chip
     constexpr int NH = FRT_RING_HALVES;
     __shared__ __attribute__((aligned(16))) C ring_lds[RING ? GPB * NH * (M / 2) : 1];      // per lane group: NH half-frames of M/2 complex
@@ -198,7 +205,7 @@ stft_kernel(const StftArgs a) {
     // instead of the vector ALUs this kernel is bound by
     const int grp = TPF == 64 ? __builtin_amdgcn_readfirstlane(tid / TPF) : tid / TPF;
     const int i = tid - grp * TPF;
-    C* buf = lds + grp * lds_padded_size(M);
+    C* buf = lds + grp * Lay::size(M);
 
     const int gg = blockIdx.x * GPB + grp;
     const bool group_ok = gg < a.n_groups;
@@ -245,6 +252,19 @@ stft_kernel(const StftArgs a) {
     // clip((10 log10(P + eps) + w - min)/(max - min), 0, 1) * 255 up to float rounding
     const T* wgt = (const T*)(a.kind == FRT_STFT_IMAGE ? a.wimage : a.weight);
     const T image_gain = (T)a.image_gain;
+    static_assert(!SPLIT || WAVE, "split rows: N <= 1024");
+    constexpr int PITCH = SPLIT ? M : M + 1;            // values per output row
+    constexpr bool NYQ_REG = SPLIT && TPF == 64;        // lane g of these registers holds frame g's Nyquist value until the run ends
+    // IMAGE kind of the NYQ_REG instances: EIGHT colour values per lane and frame.  Lane 0's descending-side powers move into the
+    // slots its stores write (bins M - 64 (j + 1): slots 5, 6, 7 and the self-paired bin M/2) before the epilogue, its hoisted
+    // weights are those bins', and the Nyquist POWER waits in the per-run register: its colour is found once per run, behind the
+    // frame loop.  Every other kind and instance evaluates nine values (the ninth, bin M/2, is lane 0's alone).
+    // (The register-window instances only.  SHIFT = 0 reloads the whole frame per hop and sits at its 168 registers: built with the
+    // eight-value path it spilled two registers, 12 bytes of scratch per lane, where the nine-value path has none.  The ring
+    // instance serves the colour kind in experiment builds only, and its code behind the frame loop stays the one plain store.)
+    constexpr bool EIGHT_INST = NYQ_REG && SHIFT > 0;
+    const bool eight = EIGHT_INST && a.kind == FRT_STFT_IMAGE;
+    const int ihi_w = (eight && i == 0) ? TPF : i;      // descending side: the weights of bins M - ihi_w - j TPF
     TwRegs<T, LOG2M> twr;
     if constexpr (HOIST) {
 #pragma unroll
@@ -257,7 +277,7 @@ stft_kernel(const StftArgs a) {
             if constexpr (!TLDS) twu[j] = twn[i + j * TPF];
             if constexpr (!WLDS) {
                 wdb[j] = wgt ? wgt[i + j * TPF] : (T)0;
-                wdb[4 + j] = wgt ? wgt[M - i - j * TPF] : (T)0;
+                wdb[4 + j] = wgt ? wgt[M - ihi_w - j * TPF] : (T)0;
             }
         }
         twr.load((const C*)a.tw, i);
@@ -267,10 +287,20 @@ stft_kernel(const StftArgs a) {
     }
 
     const T norm_off = (T)a.norm_off, norm_scale = (T)a.norm_scale;
-    static_assert(!SPLIT || WAVE, "split rows: N <= 1024");
-    constexpr int PITCH = SPLIT ? M : M + 1;            // values per output row
-    constexpr bool NYQ_REG = SPLIT && TPF == 64;        // lane g of these registers holds frame g's Nyquist value until the run ends
     uint32_t nyq_lo = 0, nyq_hi = 0;
+
+    // colour-index value of a power (IMAGE kind).  float32: with the dB floor below the LUT's range everywhere, P + 1e-30 rounds
+    // to P for every P that is not clamped to index 0 anyway, and the add is left out (eps_free, frt_stft_set_epilogue).
+    // float64 instance: the same float32 evaluation of the index from the power rounded to float32 (its own 2^-24 is inside
+    // `thr`), the float64 comparison for the few bins next to an edge — no float64 logarithm (software, ~40 instructions) per bin
+    const float gain32 = (float)image_gain;
+    auto index_value = [&](auto eps_free, T pw, T w) -> float {
+        float wf;
+        if constexpr (sizeof(T) == 8) wf = (float)(w + (T)a.image_thr);
+        else wf = (float)w;
+        if constexpr (decltype(eps_free)::value) return clamp_index(gain32 * __log2f((float)pw) + wf);
+        else return clamp_index(gain32 * __log2f((float)pw + 1e-30f) + wf);
+    };
 
     typedef T tv2 __attribute__((ext_vector_type(2)));     // a slot stays ONE 64-bit register pair from the load to the window multiply
     auto load_slot = [&](long long f, int j) -> tv2 {
@@ -429,10 +459,10 @@ stft_kernel(const StftArgs a) {
         } else
 #endif
         if constexpr (HOIST) {
-            fft_pow2_forward<T, LOG2M, WAVE>(v, buf, i, twr);
+            fft_pow2_forward<T, LOG2M, WAVE, Lay>(v, buf, i, twr);
         } else {
             TwTable<T, LOG2M> twt{(const C*)a.tw, zero};
-            fft_pow2_forward<T, LOG2M, WAVE>(v, buf, i, twt);
+            fft_pow2_forward<T, LOG2M, WAVE, Lay>(v, buf, i, twt);
         }
 
         // ---- conjugate-symmetric unpack, two bins at a time ------------------------------------------
@@ -507,7 +537,10 @@ stft_kernel(const StftArgs a) {
             const int klo = i, khi = M - i;
             T* row = outc + (f0 + g) * PITCH;
             // the frame's nine values: vals[j] = bin klo + j TPF, vals[4 + j] = bin khi - j TPF, mid = bin M/2 (lane 0 of the group)
-            auto store_row = [&](auto* r, const auto* vals, auto mid) {
+            // permuted (eight-value colour rows): lane 0's vals[4..7] already are the values its descending stores write, and the
+            // Nyquist bin is not among them
+            auto store_row = [&](auto* r, const auto* vals, auto mid, auto permuted) {
+                constexpr bool PERMUTED = decltype(permuted)::value;
                 if constexpr (!SPLIT) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
@@ -527,7 +560,9 @@ stft_kernel(const StftArgs a) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         auto hv = vals[4 + j];
-                        if (i == 0) hv = j < 3 ? vals[5 + (j < 3 ? j : 0)] : mid;
+                        if constexpr (!PERMUTED) {
+                            if (i == 0) hv = j < 3 ? vals[5 + (j < 3 ? j : 0)] : mid;
+                        }
 #ifdef FRT_SPLIT_PLAIN_STORES
                         stream_store(r + klo + j * TPF, vals[j]);
                         stream_store(r + M - ihi - j * TPF, hv);
@@ -537,7 +572,8 @@ stft_kernel(const StftArgs a) {
 #endif
                     }
                     // bin M (lane 0, slot 4)
-                    if constexpr (NYQ_REG) {
+                    if constexpr (PERMUTED) {
+                    } else if constexpr (NYQ_REG) {
                         nyq_lo = lane_insert(nyq_lo, value_bits_lo(vals[4]), g & 63, i);
                         if constexpr (sizeof(*vals) == 8) nyq_hi = lane_insert(nyq_hi, value_bits_hi(vals[4]), g & 63, i);
                     } else if (i == 0) {
@@ -546,14 +582,14 @@ stft_kernel(const StftArgs a) {
                 }
             };
             if (a.kind == FRT_STFT_PSD) {
-                store_row(row, res, res_mid);
+                store_row(row, res, res_mid, std::false_type{});
             } else {
                 T wl[4], wh[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if constexpr (WLDS) {
                         wl[j] = wgt_lds[klo + j * TPF];
-                        wh[j] = wgt_lds[khi - j * TPF];
+                        wh[j] = wgt_lds[M - ihi_w - j * TPF];
                     } else if constexpr (HOIST) {
                         wl[j] = wdb[j];
                         wh[j] = wdb[4 + j];
@@ -566,76 +602,101 @@ stft_kernel(const StftArgs a) {
                 if (a.kind == FRT_STFT_IMAGE) {
                     // colour words are 4 bytes whatever the arithmetic type
                     uint32_t* prow = (uint32_t*)a.out + chan * a.out_cstride + (f0 + g) * PITCH;
-                    // float32: with the dB floor below the LUT's range everywhere, P + 1e-30 rounds to P for every P that
-                    // is not clamped to index 0 anyway, and the add is left out (eps_free, frt_stft_set_epilogue)
-                    auto colour_row = [&](auto eps_free) {
-                        constexpr bool EPS_FREE = decltype(eps_free)::value;
-                        // float64 instance: the same float32 evaluation of the index from the power rounded to float32 (its own
-                        // 2^-24 is inside `thr`), the float64 comparison for the few bins next to an edge — no float64 logarithm
-                        // (software, ~40 instructions) per bin
-                        const float gain32 = (float)image_gain;
-                        auto index_value = [&](T pw, T w) -> float {
-                            float wf;
-                            if constexpr (sizeof(T) == 8) wf = (float)(w + (T)a.image_thr);
-                            else wf = (float)w;
-                            if constexpr (EPS_FREE) return clamp_index(gain32 * __log2f((float)pw) + wf);
-                            else return clamp_index(gain32 * __log2f((float)pw + 1e-30f) + wf);
-                        };
-                        float q[9];
-                        uint32_t colour[9];
+                    auto colour_row = [&](auto eps_free, auto eight_c) {
+                        constexpr bool EIGHT = decltype(eight_c)::value;
+                        constexpr int NV = EIGHT ? 8 : 9;                       // values a lane evaluates
+                        if constexpr (EIGHT) {
+                            // lane g keeps frame g's Nyquist POWER (lane 0, slot 4) for the end of the run; then lane 0's slots 4..7
+                            // take the powers of the bins it stores there
+                            nyq_lo = lane_insert(nyq_lo, value_bits_lo(res[4]), g & 63, i);
+                            if constexpr (sizeof(T) == 8) nyq_hi = lane_insert(nyq_hi, value_bits_hi(res[4]), g & 63, i);
+                            if (i == 0) {
+                                res[4] = res[5];
+                                res[5] = res[6];
+                                res[6] = res[7];
+                                res[7] = res_mid;
+                            }
+                        }
+                        // power and weight of value j; j = 8: bin M/2, stored by thread 0 only
+                        auto power = [&](int j) -> T { return j < 8 ? res[j] : res_mid; };
+                        auto wof = [&](int j) -> T { return j < 4 ? wl[j] : j < 8 ? wh[j - 4] : wdb_mid; };
+                        float q[NV];
+                        uint32_t colour[NV];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            q[j] = index_value(res[j], wl[j]);
-                            q[4 + j] = index_value(res[4 + j], wh[j]);
+                            q[j] = index_value(eps_free, res[j], wl[j]);
+                            q[4 + j] = index_value(eps_free, res[4 + j], wh[j]);
                         }
-                        q[8] = index_value(res_mid, wdb_mid);               // stored by thread 0 only
+                        if constexpr (!EIGHT) {
+                            q[8] = index_value(eps_free, res_mid, wdb_mid);
+#ifdef FRT_ABLATE
+                            if (a.ablate & 16) q[8] = 0.5f;
+#endif
+                        }
 #pragma unroll
-                        for (int j = 0; j < 9; ++j) colour[j] = lut_lds[(int)q[j]];
+                        for (int j = 0; j < NV; ++j) colour[j] = lut_lds[(int)q[j]];
                         {
                             // Bins within 2 thr above an index edge (3e-4 of them) are decided in float64 (exact_colour_index).
                             // The LUT reads above are issued first, with the float32 index, so that the frame's only branch
                             // sits behind them and in front of nothing but the stores; the rare path recomputes what it
-                            // needs from the powers (nothing but those nine values and the colours stays live across it).
-                            float fmin9 = i == 0 ? __builtin_amdgcn_fractf(q[8]) : 1.f;
+                            // needs from the powers (nothing but those values and the colours stays live across it).
+                            float fmin9;
+                            if constexpr (EIGHT) {
+                                // eight fracts: three three-input minima and one two-input
+                                auto fr = [&](int j) { return __builtin_amdgcn_fractf(q[j]); };
+                                fmin9 = __builtin_fminf(__builtin_fminf(fr(0), fr(1)), fr(2));
+                                fmin9 = __builtin_fminf(__builtin_fminf(fmin9, fr(3)), fr(4));
+                                fmin9 = __builtin_fminf(__builtin_fminf(fmin9, fr(5)), fr(6));
+                                fmin9 = __builtin_fminf(fmin9, fr(7));
+                            } else {
+                                fmin9 = i == 0 ? __builtin_amdgcn_fractf(q[8]) : 1.f;
 #pragma unroll
-                            for (int j = 0; j < 8; ++j) fmin9 = fminf(fmin9, __builtin_amdgcn_fractf(q[j]));
+                                for (int j = 0; j < 8; ++j) fmin9 = fminf(fmin9, __builtin_amdgcn_fractf(q[j]));
+                            }
                             if (__any(fmin9 < a.edge2)) {
                                 // ONE instance of the float64 decision: every lane with such a bin picks its first one
-                                // (select chains over the nine register slots), the wave serves those lanes one after the
+                                // (select chains over the register slots), the wave serves those lanes one after the
                                 // other (exact_colour_index), and the colour goes back through a select chain; a lane with
                                 // two such bins in one frame (1e-5 of the frames) goes round again.
                                 // (the index values are recomputed from the powers here — bit-identical, same operations —
-                                // so that only the nine powers, not the nine index values as well, stay live across the branch)
+                                // so that only the powers, not the index values as well, stay live across the branch)
                                 uint32_t pend = 0;
-                                auto power = [&](int j) -> T { return j < 8 ? res[j] : res_mid; };
 #pragma unroll
                                 for (int j = 0; j < 4; ++j) {
-                                    pend |= (__builtin_amdgcn_fractf(index_value(power(j), wl[j])) < a.edge2 ? 1u : 0u) << j;
-                                    pend |= (__builtin_amdgcn_fractf(index_value(power(4 + j), wh[j])) < a.edge2 ? 1u : 0u) << (4 + j);
+                                    pend |= (__builtin_amdgcn_fractf(index_value(eps_free, power(j), wl[j])) < a.edge2 ? 1u : 0u) << j;
+                                    pend |= (__builtin_amdgcn_fractf(index_value(eps_free, power(4 + j), wh[j])) < a.edge2 ? 1u : 0u) << (4 + j);
                                 }
-                                if (i == 0) pend |= (__builtin_amdgcn_fractf(index_value(power(8), wdb_mid)) < a.edge2 ? 1u : 0u) << 8;
+                                if constexpr (!EIGHT) {
+                                    if (i == 0) pend |= (__builtin_amdgcn_fractf(index_value(eps_free, power(8), wof(8))) < a.edge2 ? 1u : 0u) << 8;
+                                }
 #pragma unroll 1
                                 while (__any(pend != 0)) {
                                     const int jsel = pend ? __ffs(pend) - 1 : 0;
-                                    T psel = power(8), wsel = wdb_mid;
+                                    T psel = power(NV - 1), wsel = wof(NV - 1);
 #pragma unroll
                                     for (int j = 0; j < 4; ++j) {
                                         psel = jsel == j ? res[j] : jsel == 4 + j ? res[4 + j] : psel;
                                         wsel = jsel == j ? wl[j] : jsel == 4 + j ? wh[j] : wsel;
                                     }
-                                    const float qsel = index_value(psel, wsel);
-                                    const int ksel = jsel < 4 ? klo + jsel * TPF : jsel < 8 ? khi - (jsel - 4) * TPF : M / 2;
+                                    const float qsel = index_value(eps_free, psel, wsel);
+                                    // (eight values: lane 0's descending slots hold the bins M - (j + 1) TPF)
+                                    const int ksel = jsel < 4 ? klo + jsel * TPF : jsel < 8 ? M - (EIGHT ? ihi_w : i) - (jsel - 4) * TPF : M / 2;
                                     const uint32_t c = lut_lds[exact_colour_index(pend != 0, psel, ksel, (int)qsel, a)];
 #pragma unroll
-                                    for (int j = 0; j < 9; ++j) colour[j] = (pend != 0 && jsel == j) ? c : colour[j];
+                                    for (int j = 0; j < NV; ++j) colour[j] = (pend != 0 && jsel == j) ? c : colour[j];
                                     pend &= pend - 1;
                                 }
                             }
                         }
-                        store_row(prow, colour, colour[8]);
+                        store_row(prow, colour, colour[NV - 1], eight_c);
                     };
-                    if (a.eps_free) colour_row(std::true_type{});
-                    else colour_row(std::false_type{});
+                    if constexpr (EIGHT_INST) {
+                        if (a.eps_free) colour_row(std::true_type{}, std::true_type{});
+                        else colour_row(std::false_type{}, std::true_type{});
+                    } else {
+                        if (a.eps_free) colour_row(std::true_type{}, std::false_type{});
+                        else colour_row(std::false_type{}, std::false_type{});
+                    }
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
@@ -648,7 +709,7 @@ stft_kernel(const StftArgs a) {
                         for (int j = 0; j < 8; ++j) res[j] = (res[j] + norm_off) * norm_scale;
                         res_mid = (res_mid + norm_off) * norm_scale;
                     }
-                    store_row(row, res, res_mid);
+                    store_row(row, res, res_mid, std::false_type{});
                 }
             }
         }
@@ -668,9 +729,26 @@ stft_kernel(const StftArgs a) {
     }
     if constexpr (NYQ_REG) {
         // the run's Nyquist values: lane g holds frame g's (runs are at most 64 frames, stft_launch)
+        const long long at = chan * a.n_frames + f0 + i;
+        uint32_t word = nyq_lo;                          // what a 4-byte plane receives: the value's bits, or the colour
+        if constexpr (EIGHT_INST) {
+            if (a.kind == FRT_STFT_IMAGE) {
+                // the register holds POWERS: one instance of the colour epilogue per run instead of one per frame — the same
+                // index value, edge test and float64 decision as every other bin's, with the weight of bin M (wave-uniform: a
+                // scalar load, no vector-memory operation behind the frame loop but the plane's store).  exact_colour_index
+                // returns the float32 index for the lanes that are not next to an edge: one LUT read, no branch around it
+                T pw;
+                if constexpr (sizeof(T) == 8) pw = __hiloint2double((int)nyq_hi, (int)nyq_lo);
+                else pw = __uint_as_float(nyq_lo);
+                typedef const T __attribute__((address_space(4))) * wtable;
+                const T w = ((wtable)(uintptr_t)a.wimage)[M];
+                const float q = a.eps_free ? index_value(std::true_type{}, pw, w) : index_value(std::false_type{}, pw, w);
+                const bool near_edge = i < nfr && __builtin_amdgcn_fractf(q) < a.edge2;
+                word = lut_lds[exact_colour_index(near_edge, pw, M, (int)q, a)];
+            }
+        }
         if (i < nfr) {
-            const long long at = chan * a.n_frames + f0 + i;
-            if (a.kind == FRT_STFT_IMAGE || sizeof(T) == 4) ((uint32_t*)a.out_nyq)[at] = nyq_lo;
+            if (a.kind == FRT_STFT_IMAGE || sizeof(T) == 4) ((uint32_t*)a.out_nyq)[at] = word;
             else ((double*)a.out_nyq)[at] = __hiloint2double((int)nyq_hi, (int)nyq_lo);
         }
     }

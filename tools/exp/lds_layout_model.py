@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """LDS bank-conflict model of the exchange layouts of round 4's kernels (ola_pair_kernel, stft_pk16_kernel, stft_pk16h_kernel,
-stft_pk16q_kernel, stft_pk16w_kernel), after MI355X_MICROARCH.md §LDS: a wave64 access is serviced in fixed lane groups, one LDS
+stft_pk16q_kernel, stft_pk16w_kernel) and of the headline's one-wavefront 512-point transform (stft_wave512: fft_core.h), after MI355X_MICROARCH.md §LDS: a wave64 access is serviced in fixed lane groups, one LDS
 cycle per group when no two lanes of the group touch one bank at different addresses.
 
     instruction      lane groups                                                         bank of byte address a
@@ -159,10 +159,39 @@ def pk16w():                                  # N = 2048: 64 threads, four lanes
     return res
 
 
-KERNELS = {"ola_pair_kernel": ola_pair, "stft_pk16_kernel": pk16, "stft_pk16h_kernel": pk16h, "stft_pk16q_kernel": pk16q, "stft_pk16w_kernel": pk16w}
+# ---- stft_kernel, N = 1024: one wavefront, M = 512 complex points, three radix-8 Stockham passes, two exchanges ---------------
+def wave512_pad(x):                           # fft_core.h lds_pad: one pad slot per 8 points (576 slots)
+    return x + (x >> 3)
+
+
+def wave512_xor(x):                           # fft_core.h LdsXorWave512: bits 0-3 ^= bits 3-6 (512 slots)
+    return x ^ ((x >> 3) & 15)
+
+
+def stft_wave512(phys=wave512_xor, elem=8):
+    """The four access patterns of fft_pow2_forward<T, 9, WAVE_LOCAL>: thread i scatters its eight outputs of pass 0 to 8 i + q
+    and of pass 1 to 64 (i >> 3) + (i & 7) + 8 q, and gathers i + 64 j after either.  `phys` maps a point to its slot; elem = 16: the
+    float64 instance (ds_write_b128 / ds_read_b128 lane groups), for which the same two maps give the same degrees."""
+    wr, rd = ("write_b64", "read_b64") if elem == 8 else ("write_b128", "read_b128")
+    res = {}
+    res["exchange 1 write"] = max(worst_over_waves(wr, 64, lambda t, q=q: elem * phys(8 * t + q)) for q in range(8))
+    res["exchange 1 read"] = max(worst_over_waves(rd, 64, lambda t, j=j: elem * phys(t + 64 * j)) for j in range(8))
+    res["exchange 2 write"] = max(worst_over_waves(wr, 64, lambda t, q=q: elem * phys(64 * (t >> 3) + (t & 7) + 8 * q)) for q in range(8))
+    res["exchange 2 read"] = max(worst_over_waves(rd, 64, lambda t, j=j: elem * phys(t + 64 * j)) for j in range(8))
+    return res
+
+
+def stft_wave512_padded():
+    return stft_wave512(wave512_pad)
+
+
+KERNELS = {"stft_kernel N=1024": stft_wave512, "ola_pair_kernel": ola_pair, "stft_pk16_kernel": pk16, "stft_pk16h_kernel": pk16h, "stft_pk16q_kernel": pk16q, "stft_pk16w_kernel": pk16w}
+
+# layouts that were replaced, kept so that the model can be seen to tell them apart (not asserted conflict free)
+BEFORE = {"stft_kernel N=1024, one pad slot per 8 points": stft_wave512_padded}
 
 if __name__ == "__main__":
-    for name, fn in KERNELS.items():
+    for name, fn in list(KERNELS.items()) + list(BEFORE.items()):
         print(name)
         for k, v in fn().items():
             print(f"    {k:24s} worst conflict degree {v}")
