@@ -1,8 +1,15 @@
 """What the batch classes (LevelsBatch, ScopeBatch, CurveBatch, SpectrumBatch, SpectrogramBatch) share: their input is a float32/float64 numpy
-array or CUDA tensor, their results are of the same kind, and a recording is seen in chunks."""
+array or CUDA tensor, their results are of the same kind, and a recording is seen in chunks; for the two STFT chains, the sample
+front of run() (RecordingFront)."""
 from __future__ import annotations
 
+import ctypes
+import math
+from contextlib import contextmanager
+
 import numpy as np
+
+from . import _lib
 
 
 def chunk_ends(T, chunk=512):
@@ -65,3 +72,101 @@ def alloc(like, shape, dtype=np.float64, zero=False):
         return getattr(np, name)(shape, dtype)
     import torch
     return getattr(torch, name)(shape, dtype=getattr(torch, np.dtype(dtype).name), device=like.device)
+
+
+# ---- the sample front of SpectrumBatch.run and SpectrogramBatch.run --------------------------------------------------------------
+
+def check_samples(who, x, state, dual=False):
+    """(x with its stream axis, is_np, squeeze, pending) of a recording x [S, T] ([S, 2, T] with `dual`; the stream axis may be
+    left out) and a carried state (None: a fresh widget)."""
+    is_np = isinstance(x, np.ndarray)
+    if not is_np and not (type(x).__module__.startswith("torch") and x.is_cuda):
+        raise TypeError(f"{who}.run takes a numpy array or a CUDA tensor")
+    full = 3 if dual else 2
+    if x.ndim not in (full - 1, full):
+        raise ValueError(f"expected [S, {'2, ' if dual else ''}T] (the stream axis may be left out), got {tuple(x.shape)}")
+    if str(x.dtype).split(".")[-1] not in ("float32", "float64"):
+        raise TypeError(f"samples must be float32 or float64, got {x.dtype}")
+    squeeze = x.ndim == full - 1
+    if squeeze:
+        x = x[None]
+    if dual and x.shape[1] != 2:
+        raise ValueError(f"dual channels need two rows per stream, got {x.shape[1]}")
+    return x, is_np, squeeze, 0 if state is None else int(state.pending)
+
+
+@contextmanager
+def null_stream(x, is_np):
+    """The batch kernels launch on the null stream (friture_hip.h): inside, everything is enqueued there, after whatever the
+    caller's stream still has to do to x; afterwards the caller's stream may read the results.  Yields the device."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device()) if is_np else x.device
+    mine, null = torch.cuda.current_stream(dev), torch.cuda.default_stream(dev)
+    if mine != null:
+        mine.synchronize()
+    with torch.cuda.device(dev), torch.cuda.stream(null):
+        yield dev
+    if mine != null:
+        null.synchronize()
+
+
+class RecordingFront:
+    """The samples of a recording x [S, (rows,) T] behind a carried tail, as C = S * rows device rows, and the frames of a
+    schedule transformed from them slab by slab.  To be made and used inside null_stream: making it stages x, load_tail the
+    tail (a step of its own, so that each class keeps the order in which its state reaches the stream)."""
+
+    def __init__(self, x, is_np, dev, pending, fft_size, hop, frame_start, ends=None):
+        import torch
+        self.torch, self.dev, self.N, self.hop, self.frame_start = torch, dev, fft_size, hop, frame_start
+        self.C, self.L, self.F, self.T = math.prod(x.shape[:-1]), fft_size + pending, int(frame_start[-1]), x.shape[-1]
+        if ends is not None:                                        # the widgets were pushed ends[-1] samples
+            self.T = int(np.asarray(ends).reshape(-1)[-1]) if np.size(ends) else 0
+        self.x = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) if is_np else x).reshape(self.C, x.shape[-1])
+        if self.x.stride(1) != 1:
+            self.x = self.x.contiguous()
+
+    def load_tail(self, tail):
+        """The carried tail (None: zeros), copied: the caller's state is not modified."""
+        if tail is None:
+            self.tail = self.torch.zeros((self.C, self.L), dtype=self.torch.float64, device=self.dev)
+        else:
+            self.tail = self.torch.as_tensor(tail).to(device=self.dev, dtype=self.torch.float64).reshape(self.C, self.L).contiguous()
+
+    def window(self, a, b):
+        """Samples [a, b) of tail || x per row as float64 (float32 widens exactly), unit stride along time."""
+        x, L = self.x, self.L
+        if a >= L and x.dtype == self.torch.float64:
+            return x[:, a - L:b - L]
+        out = self.torch.empty((self.C, b - a), dtype=self.torch.float64, device=self.dev)
+        if a < L:
+            out[:, :min(b, L) - a] = self.tail[:, a:min(b, L)]
+        if b > L:
+            out[:, max(a, L) - a:] = x[:, max(a, L) - L:b - L]
+        return out
+
+    def transform(self, eng, kind, n_bins, scratch_bytes, f_lo=0):
+        """The frames from f_lo on, in time slabs of whole refreshes r0 .. r1 - 1, at most scratch_bytes of float64 frames each
+        (one refresh if it alone has more; slabs that end at or before f_lo drop out).  Per slab: one frt_stft_run of `kind` over
+        its frames fa .. fb - 1 on the null stream into a scratch buffer [C, fb - fa, n_bins] (sized for the largest slab, freed
+        when the loop ends), then yields (r0, r1, fa, fb, the buffer's address)."""
+        lib, vp, fs = _lib.init(), ctypes.c_void_p, self.frame_start
+        _lib.check(lib.frt_stft_set_stream(eng._h, None))
+        fmax = max(1, int(scratch_bytes) // (self.C * n_bins * 8))
+        slabs, r0 = [], 0
+        while r0 < len(fs) - 1:
+            r1 = max(r0 + 1, int(np.searchsorted(fs, fs[r0] + fmax, "right")) - 1)
+            if fs[r1] > f_lo:
+                slabs.append((r0, r1, max(int(fs[r0]), f_lo), int(fs[r1])))
+            r0 = r1
+        out = self.torch.empty(self.C * n_bins * max(fb - fa for _, _, fa, fb in slabs), dtype=self.torch.float64, device=self.dev)
+        nfo = ctypes.c_int64(0)
+        for r0, r1, fa, fb in slabs:
+            seg = self.window(fa * self.hop, (fb - 1) * self.hop + self.N)
+            _lib.check(lib.frt_stft_run(eng._h, kind, vp(seg.data_ptr()), seg.shape[1], seg.stride(0) if self.C > 1 else seg.shape[1],
+                                        vp(out.data_ptr()), ctypes.byref(nfo)))
+            assert nfo.value == fb - fa
+            yield r0, r1, fa, fb, vp(out.data_ptr())
+
+    def new_tail(self):
+        """(tail [C, fft_size + pending] float64, pending) behind the schedule's last frame: what the next call carries in."""
+        return self.window(self.F * self.hop, self.L + self.T).clone(), self.L + self.T - self.F * self.hop - self.N

@@ -11,7 +11,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from ._batchio import frame_schedule
+from ._batchio import RecordingFront, check_samples, frame_schedule, null_stream
 from .audioproc import audioproc
 from .constants import SAMPLING_RATE
 from .plotting import frequency_scales as fscales
@@ -24,7 +24,6 @@ from .stft import StftEngine
 
 DEFAULT_FFT_SIZE = 4096        # spectrogram_settings.py:27-34
 DEFAULT_TIMERANGE = 10.
-
 
 
 def _torch_device():
@@ -292,118 +291,65 @@ class SpectrogramBatch:
 
     # ---- device ---------------------------------------------------------------------------------------------------------------
     def _check_input(self, x, state):
-        is_np = isinstance(x, np.ndarray)
-        if not is_np and not (type(x).__module__.startswith("torch") and x.is_cuda):
-            raise TypeError("SpectrogramBatch.run takes a numpy array or a CUDA tensor")
-        if x.ndim not in (1, 2):
-            raise ValueError(f"expected [S, T] (the stream axis may be left out), got {tuple(x.shape)}")
-        if str(x.dtype).split(".")[-1] not in ("float32", "float64"):
-            raise TypeError(f"samples must be float32 or float64, got {x.dtype}")
-        squeeze = x.ndim == 1
-        if squeeze:
-            x = x[None]
-        S, T = x.shape
+        x, is_np, squeeze, pending = check_samples("SpectrogramBatch", x, state)
+        S = x.shape[0]
         if S < 1:
             raise ValueError("no stream")
-        pending = 0
         if state is not None:
-            pending = int(state.pending)
             want_tail, want_old = (S, self.fft_size + pending), (S, self.screen_height)
             if pending < 0 or tuple(state.tail.shape) != want_tail or tuple(state.old_column.shape) != want_old:
                 raise ValueError(f"state of another shape: tail {tuple(state.tail.shape)} (want {want_tail}), old_column "
                                  f"{tuple(state.old_column.shape)} (want {want_old}), pending {pending}")
-        return x, is_np, squeeze, S, T, pending
+        return x, is_np, squeeze, pending
 
     def run(self, x, chunk=512, ends=None, state=None, keep="all", scratch_bytes=1 << 30):
         if keep not in ("all", "screen"):
             raise ValueError(f"keep={keep!r} ('all' or 'screen')")
-        x, is_np, squeeze, S, T, pending = self._check_input(x, state)
+        x, is_np, squeeze, pending = self._check_input(x, state)
+        S, T = x.shape
         frame_start, refresh_chunk = self.schedule(T, chunk, ends, state)
         table = self.columns(T, chunk, ends, state)                 # raises before anything is enqueued
-        if ends is not None:                                        # the widgets were pushed ends[-1] samples
-            T = int(np.asarray(ends).reshape(-1)[-1]) if np.size(ends) else 0
         import ctypes
 
         import torch
 
         from . import _lib
         lib = _lib.init()
-        dev = torch.device("cuda", torch.cuda.current_device()) if is_np else x.device
-        B, N, hop, H = self.n_bins, self.fft_size, self.hop, self.screen_height
-        R, F, L, P = len(refresh_chunk), int(frame_start[-1]), N + pending, len(table.src)
+        B, H = self.n_bins, self.screen_height
+        R, F, P = len(refresh_chunk), int(frame_start[-1]), len(table.src)
         c_lo = 0 if keep == "all" else max(0, P - self.screen_width)                 # the first column produced
         f_lo = 0 if keep == "all" else (max(0, int(table.src[c_lo]) - 1) if c_lo < P else max(0, F - 1))   # the first frame transformed
         Po = P - c_lo
         col_start = np.searchsorted(table.column_refresh, np.arange(R + 1))          # the columns of each refresh
         src = np.where(table.filler, -1, table.src)
         f64, vp = torch.float64, ctypes.c_void_p
-        # frt_specgram_batch launches on the null stream (friture_hip.h): everything here is enqueued there, after whatever the
-        # caller's stream still has to do to x
-        mine, null = torch.cuda.current_stream(dev), torch.cuda.default_stream(dev)
-        if mine != null:
-            mine.synchronize()
-        with torch.cuda.device(dev), torch.cuda.stream(null):
-            xd = torch.from_numpy(np.ascontiguousarray(x)).to(dev) if is_np else x
-            if xd.stride(1) != 1:
-                xd = xd.contiguous()
+        with null_stream(x, is_np) as dev:
+            front = RecordingFront(x, is_np, dev, pending, self.fft_size, self.hop, frame_start, ends)
+            front.load_tail(None if state is None else state.tail)
             if state is None:
-                tail = torch.zeros((S, L), dtype=f64, device=dev)
                 old = torch.zeros((S, H), dtype=f64, device=dev)
-            else:                                                    # copies: the caller's state is not modified
-                tail = torch.as_tensor(state.tail).to(device=dev, dtype=f64).reshape(S, L).contiguous()
+            else:                                                    # a copy: the caller's state is not modified
                 old = torch.as_tensor(state.old_column).to(device=dev, dtype=f64).reshape(S, H).clone()
-
-            def window(a, b):
-                """Samples [a, b) of tail || x per stream as float64 (float32 widens exactly), unit stride along time."""
-                if a >= L and xd.dtype == f64:
-                    return xd[:, a - L:b - L]
-                out = torch.empty((S, b - a), dtype=f64, device=dev)
-                if a < L:
-                    out[:, :min(b, L) - a] = tail[:, a:min(b, L)]
-                if b > L:
-                    out[:, max(a, L) - a:] = xd[:, max(a, L) - L:b - L]
-                return out
-
             pixels = torch.empty((S, H, Po), dtype=torch.int32, device=dev)          # uint32 words (torch has no uint32 arithmetic)
             if R:
-                eng = self._engine(S)
-                _lib.check(lib.frt_stft_set_stream(eng._h, None))
-                # time slabs: whole refreshes, at most fmax normalised frames each (one refresh if it alone has more)
-                fmax = max(1, int(scratch_bytes) // (S * B * 8))
-                slabs, r0 = [], 0
-                while r0 < R:
-                    r1 = max(r0 + 1, int(np.searchsorted(frame_start, frame_start[r0] + fmax, "right")) - 1)
-                    if frame_start[r1] > f_lo:                       # keep="screen": the slabs before the first needed frame drop out
-                        slabs.append((r0, r1))
-                    r0 = r1
-                norm = torch.empty(S * B * max(int(frame_start[b] - max(frame_start[a], f_lo)) for a, b in slabs), dtype=f64, device=dev)
                 old_next = torch.empty_like(old)
-                nfo = ctypes.c_int64(0)
-                for r0, r1 in slabs:
-                    fa, fb = max(int(frame_start[r0]), f_lo), int(frame_start[r1])
+                for r0, r1, fa, fb, norm in front.transform(self._engine(S), _lib.FRT_STFT_NORM, B, scratch_bytes, f_lo):
                     ca, cb = max(int(col_start[r0]), c_lo), max(int(col_start[r1]), c_lo)
                     nf, nc = fb - fa, cb - ca
-                    seg = window(fa * hop, (fb - 1) * hop + N)
-                    _lib.check(lib.frt_stft_run(eng._h, _lib.FRT_STFT_NORM, vp(seg.data_ptr()), seg.shape[1], seg.stride(0) if S > 1 else seg.shape[1],
-                                                vp(norm.data_ptr()), ctypes.byref(nfo)))
-                    assert nfo.value == nf
                     local = np.ascontiguousarray(np.where(src[ca:cb] < 0, -1, src[ca:cb] - fa), np.int32)
                     weights = np.ascontiguousarray(table.a[ca:cb])
                     _lib.check(lib.frt_specgram_batch(
-                        vp(norm.data_ptr()), S, nf, B, B, nf * B, self.freq.ctypes.data, self.targets.ctypes.data, H,
+                        norm, S, nf, B, B, nf * B, self.freq.ctypes.data, self.targets.ctypes.data, H,
                         local.ctypes.data if nc else None, weights.ctypes.data if nc else None, nc, vp(old.data_ptr()),
                         vp(old_next.data_ptr()), self.lut.ctypes.data, vp(pixels.data_ptr()) if nc else None, ca - c_lo, Po))
                     old, old_next = old_next, old
-                del norm
-            new_tail = window(F * hop, L + T).clone()
-            new_state = SpectrogramState(new_tail, L + T - F * hop - N, old, table.orig_index, table.resampled_index)
+            new_tail, pending = front.new_tail()
+            new_state = SpectrogramState(new_tail, pending, old, table.orig_index, table.resampled_index)
             if is_np:
                 pixels = pixels.cpu().numpy().view(np.uint32)
                 new_state = new_state._replace(tail=new_tail.cpu().numpy(), old_column=old.cpu().numpy())
             else:
                 pixels = pixels.view(torch.uint32) if hasattr(torch, "uint32") else pixels
-        if mine != null:
-            null.synchronize()
         if squeeze:
             pixels = pixels[0]
         return SpectrogramResult(pixels, table.column_refresh[c_lo:], refresh_chunk, new_state)

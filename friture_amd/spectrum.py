@@ -17,7 +17,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _lib, tables
-from ._batchio import frame_schedule
+from ._batchio import RecordingFront, check_samples, frame_schedule, null_stream
 from .audioproc import audioproc
 from .constants import SAMPLING_RATE
 from .ringbuffer import RingBuffer
@@ -261,93 +261,38 @@ class SpectrumBatch:
 
     # ---- device ---------------------------------------------------------------------------------------------------------------
     def _check_input(self, x, state):
-        is_np = isinstance(x, np.ndarray)
-        if not is_np and not (type(x).__module__.startswith("torch") and x.is_cuda):
-            raise TypeError("SpectrumBatch.run takes a numpy array or a CUDA tensor")
-        full = 3 if self.dual_channels else 2
-        if x.ndim not in (full - 1, full):
-            raise ValueError(f"expected [S, {'2, ' if self.dual_channels else ''}T] (the stream axis may be left out), got {tuple(x.shape)}")
-        if str(x.dtype).split(".")[-1] not in ("float32", "float64"):
-            raise TypeError(f"samples must be float32 or float64, got {x.dtype}")
-        squeeze = x.ndim == full - 1
-        if squeeze:
-            x = x[None]
-        if self.dual_channels and x.shape[1] != 2:
-            raise ValueError(f"dual channels need two rows per stream, got {x.shape[1]}")
-        S, T = x.shape[0], x.shape[-1]
-        pending = 0
+        x, is_np, squeeze, pending = check_samples("SpectrumBatch", x, state, self.dual_channels)
         if state is not None:
-            pending = int(state.pending)
-            want_sm, want_tail = (S, self.rows, self.n_bins), (S, self.rows, self.fft_size + pending)
+            want_sm, want_tail = (x.shape[0], self.rows, self.n_bins), (x.shape[0], self.rows, self.fft_size + pending)
             if pending < 0 or tuple(state.smoothed.shape) != want_sm or tuple(state.tail.shape) != want_tail:
                 raise ValueError(f"state of another shape: smoothed {tuple(state.smoothed.shape)} (want {want_sm}), tail "
                                  f"{tuple(state.tail.shape)} (want {want_tail}), pending {pending}")
-        return x, is_np, squeeze, S, T, pending
+        return x, is_np, squeeze, pending
 
     def run(self, x, chunk=512, ends=None, state=None, keep="all", scratch_bytes=1 << 30):
         if keep not in ("all", "last"):
             raise ValueError(f"keep={keep!r} ('all' or 'last')")
-        x, is_np, squeeze, S, T, pending = self._check_input(x, state)
-        frame_start, refresh_chunk = self.schedule(T, chunk, ends, state)
-        if ends is not None:                                        # the widgets were pushed ends[-1] samples
-            T = int(np.asarray(ends).reshape(-1)[-1]) if np.size(ends) else 0
+        x, is_np, squeeze, pending = self._check_input(x, state)
+        frame_start, refresh_chunk = self.schedule(x.shape[-1], chunk, ends, state)
         import torch
         lib = _lib.init()
-        dev = torch.device("cuda", torch.cuda.current_device()) if is_np else x.device
-        rows, B, N, hop = self.rows, self.n_bins, self.fft_size, self.hop
-        C, R, F, L = S * rows, len(refresh_chunk), int(frame_start[-1]), N + pending
+        S, rows, B, R = x.shape[0], self.rows, self.n_bins, len(refresh_chunk)
         f64, vp = torch.float64, ctypes.c_void_p
-        # frt_spectrum_batch launches on the null stream (friture_hip.h): everything here is enqueued there, after whatever the
-        # caller's stream still has to do to x
-        mine, null = torch.cuda.current_stream(dev), torch.cuda.default_stream(dev)
-        if mine != null:
-            mine.synchronize()
-        with torch.cuda.device(dev), torch.cuda.stream(null):
-            xd = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) if is_np else x).reshape(C, x.shape[-1])
-            if xd.stride(1) != 1:
-                xd = xd.contiguous()
+        with null_stream(x, is_np) as dev:
+            front = RecordingFront(x, is_np, dev, pending, self.fft_size, self.hop, frame_start, ends)
             if state is None:
                 sm = torch.zeros((S, rows, B), dtype=f64, device=dev)
-                tail = torch.zeros((C, L), dtype=f64, device=dev)
-            else:                                                    # copies: the caller's state is not modified
+            else:                                                    # a copy: the caller's state is not modified
                 sm = torch.as_tensor(state.smoothed).to(device=dev, dtype=f64).reshape(S, rows, B).clone()
-                tail = torch.as_tensor(state.tail).to(device=dev, dtype=f64).reshape(C, L).contiguous()
-
-            def window(a, b):
-                """Samples [a, b) of tail || x per row as float64 (float32 widens exactly), unit stride along time."""
-                if a >= L and xd.dtype == f64:
-                    return xd[:, a - L:b - L]
-                out = torch.empty((C, b - a), dtype=f64, device=dev)
-                if a < L:
-                    out[:, :min(b, L) - a] = tail[:, a:min(b, L)]
-                if b > L:
-                    out[:, max(a, L) - a:] = xd[:, max(a, L) - L:b - L]
-                return out
-
+            front.load_tail(None if state is None else state.tail)
             Ro = R if keep == "all" else min(R, 1)
             db = torch.empty((S, Ro, B), dtype=f64, device=dev)
             peak = torch.empty((S, Ro), dtype=torch.int32, device=dev)
             pitch = torch.empty((S, Ro), dtype=torch.int32, device=dev)
             if R:
                 wd = None if self.dual_channels else self._table(dev, "w", self.w)
-                eng = self._engine(C)
-                _lib.check(lib.frt_stft_set_stream(eng._h, None))
-                # time slabs: whole refreshes, at most fmax frames of PSD each (one refresh if it alone has more)
-                fmax = max(1, int(scratch_bytes) // (C * B * 8))
-                slabs, r0 = [], 0
-                while r0 < R:
-                    r1 = max(r0 + 1, int(np.searchsorted(frame_start, frame_start[r0] + fmax, "right")) - 1)
-                    slabs.append((r0, r1))
-                    r0 = r1
-                psd = torch.empty(C * B * max(int(frame_start[b] - frame_start[a]) for a, b in slabs), dtype=f64, device=dev)
-                nfo = ctypes.c_int64(0)
-                for r0, r1 in slabs:
-                    fa, fb = int(frame_start[r0]), int(frame_start[r1])
+                for r0, r1, fa, fb, psd in front.transform(self._engine(S * rows), _lib.FRT_STFT_PSD, B, scratch_bytes):
                     nf, nr = fb - fa, r1 - r0
-                    seg = window(fa * hop, (fb - 1) * hop + N)
-                    _lib.check(lib.frt_stft_run(eng._h, _lib.FRT_STFT_PSD, vp(seg.data_ptr()), seg.shape[1], seg.stride(0) if C > 1 else seg.shape[1],
-                                                vp(psd.data_ptr()), ctypes.byref(nfo)))
-                    assert nfo.value == nf
                     local = np.ascontiguousarray(frame_start[r0:r1 + 1] - fa)
                     if keep == "all":
                         pk = torch.empty((S, nr), dtype=torch.int32, device=dev)
@@ -356,23 +301,20 @@ class SpectrumBatch:
                     else:
                         pk, pt, dbp, ld_db = peak, pitch, db.data_ptr(), 0
                     _lib.check(lib.frt_spectrum_batch(
-                        vp(psd.data_ptr()), 1, S, rows, nf, B, B, nf * B, local.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nr,
+                        psd, 1, S, rows, nf, B, B, nf * B, local.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nr,
                         self.kernel.ctypes.data, len(self.kernel), float(self.alpha), None if wd is None else vp(wd.data_ptr()),
                         vp(sm.data_ptr()), int(keep == "last"), vp(dbp), ld_db, vp(pk.data_ptr()), vp(pt.data_ptr())))
                     if keep == "all":
                         peak[:, r0:r1], pitch[:, r0:r1] = pk, pt
-                del psd
-            new_tail = window(F * hop, L + T).clone().reshape(S, rows, L + T - F * hop)
-            new_state = SpectrumState(sm, new_tail, L + T - F * hop - N)
+            new_tail, pending = front.new_tail()
+            new_state = SpectrumState(sm, new_tail.reshape(S, rows, new_tail.shape[1]), pending)
             if is_np:
                 db, peak, pitch = db.cpu().numpy(), peak.cpu().numpy(), pitch.cpu().numpy()
                 fmax_hz, fpitch_hz = self.freq[peak], np.maximum(self.freq[pitch], 1e-20)
-                new_state = SpectrumState(sm.cpu().numpy(), new_tail.cpu().numpy(), new_state.pending)
+                new_state = SpectrumState(sm.cpu().numpy(), new_state.tail.cpu().numpy(), pending)
             else:
                 fd = self._table(dev, "freq", self.freq)
                 fmax_hz, fpitch_hz = fd[peak.long()], torch.clamp_min(fd[pitch.long()], 1e-20)
-        if mine != null:
-            null.synchronize()
         if squeeze:
             db, peak, pitch, fmax_hz, fpitch_hz = db[0], peak[0], pitch[0], fmax_hz[0], fpitch_hz[0]
         return SpectrumResult(db, peak, pitch, fmax_hz, fpitch_hz, refresh_chunk, new_state)

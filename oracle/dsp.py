@@ -586,6 +586,25 @@ class MirrorRing:
         self.buffer, self.buffer_length = nb, new
 
 
+def widget_frames(x, ends, fft_size, needed):
+    """The frame bookkeeping that the spectrum and the spectrogram widget share (friture/spectrum.py:133-155,
+    friture/spectrogram.py:131-160): x [rows, T] float64 pushed chunk by chunk (`ends`: the chunks' end indices) into a
+    ring sized to lose nothing; a chunk after which realizable = floor((offset - old_index) / needed) > 0 yields
+    (its index, frames [realizable, rows, fft_size]): data_indexed(old_index, fft_size) per frame, old_index += int(needed)."""
+    hop = int(needed)
+    biggest = int(np.max(np.diff(np.concatenate([[0], ends])))) if len(ends) else 0
+    ring, old_index, pos = MirrorRing(max(10000, 2 * (fft_size + hop + biggest))), 0, 0
+    for c, e in enumerate(ends):
+        ring.push(x[:, pos:e])
+        pos = int(e)
+        realizable = int(np.floor((ring.offset - old_index) / needed))
+        if realizable <= 0:
+            continue
+        frames = np.stack([ring.data_indexed(old_index + i * hop, fft_size) for i in range(realizable)])
+        old_index += realizable * hop
+        yield c, frames
+
+
 # --------------------------------------------------------------------------------------------
 # P5 / P6: screen-space resamplers of the spectrogram
 # --------------------------------------------------------------------------------------------

@@ -1,37 +1,25 @@
-"""Record tests/golden/spectrogrambatch/<case>.npz from the unmodified reference, or check the committed files.
+"""Record tests/golden/spectrogrambatch/<case>.npz from the reference's own spectrogram classes.
 
-    python tools/record_spectrogrambatch_golden.py            # record
-    python tools/record_spectrogrambatch_golden.py --check    # record into memory, compare with the committed arrays
-
-Needs the reference checkout (oracle/refshim.py).  The reference's own classes do the work: audioproc, RingBuffer (behind
-refshim.AudioBuffer), Frequency_Resampler, Online_Linear_2D_resampler, Color_Transform and Transform_Pipeline, set up as
+Driven by oracle/make_golden.py (needs the reference checkout).  The reference's own classes do the work: audioproc, RingBuffer
+(behind refshim.AudioBuffer), Frequency_Resampler, Online_Linear_2D_resampler, Color_Transform and Transform_Pipeline, set up as
 Spectrogram_Widget.__init__ sets them up and driven by the statements of Spectrogram_Widget.handle_new_data
 (friture/spectrogram.py:131-173) with the widget's Qt parts (the image item, the settings dialog) left out.  The column table is
 read off the reference, not restated: the time resampler calls linear_interp_2D once per frame that emits columns, and a
 wrapper around that function notes the frame (orig_index counts them) and obtains the weights from the function itself (old = 1,
 new = 0 gives `a`); columns of a push's block beyond what those calls wrote are the fillers.
 
-Per case of tests/spectrogrambatch_helpers.GOLDEN_CASES one file holds x (float32 PCM), ends, norm [F, B], frame_start,
-refresh_chunk, pixels [H, P] (flipped as the image item flips them), src, a, filler, column_refresh, targets, weight and lut.
-The files live in a folder of their own: oracle/make_golden.py owns the .npz files directly under tests/golden/ (its --check
-fails on a file there that none of its recorders writes), and one file per case keeps each below 1 MiB.
+Per case of oracle.spectrogrambatch.GOLDEN_CASES one file holds x (float32 PCM), ends, norm [F, B], frame_start, refresh_chunk,
+pixels [H, P] (flipped as the image item flips them), src, a, filler, column_refresh, targets, weight and lut.  One file per case,
+in a folder of their own, keeps each below 1 MiB.
 """
 from __future__ import annotations
 
-import argparse
-import sys
 from fractions import Fraction
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path[:0] = [str(ROOT), str(ROOT / "tests")]
-
-from oracle import refshim  # noqa: E402
-import spectrogrambatch_helpers as H  # noqa: E402
-
-FOLDER = ROOT / "tests" / "golden" / "spectrogrambatch"
+from . import refshim
+from . import spectrogrambatch as H
 
 
 def record_case(case):
@@ -138,42 +126,12 @@ def record_case(case):
                 weight=np.broadcast_to(w[:, 0], freq.shape).astype(np.float64)), lut
 
 
-def record():
+def spectrogrambatch(out_dir):
     refshim.install()
-    files = {}
+    folder = out_dir / H.GOLDEN_FOLDER
+    folder.mkdir(exist_ok=True)
     for name, case in H.GOLDEN_CASES.items():
         got, lut = record_case(case)
         got["lut"] = np.asarray(lut, np.uint32)
-        files[name] = got
         print(f"{name}: {got['norm'].shape[0]} frames, {got['pixels'].shape[1]} columns, {int(got['filler'].sum())} fillers")
-    return files
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--check", action="store_true", help="compare with the committed files instead of replacing them")
-    args = ap.parse_args()
-    if not refshim.available():
-        sys.exit(f"reference checkout not found at {refshim.REFERENCE_ROOT}")
-    files = record()
-    if not args.check:
-        FOLDER.mkdir(parents=True, exist_ok=True)
-        for name, arrays in files.items():
-            np.savez_compressed(FOLDER / f"{name}.npz", **arrays)
-            print(f"written to {(FOLDER / f'{name}.npz').relative_to(ROOT)} ({(FOLDER / f'{name}.npz').stat().st_size} bytes)")
-        return 0
-    from oracle.make_golden import difference, load
-    failed = sorted({p.stem for p in FOLDER.glob("*.npz")} - set(files))
-    for name in failed:
-        print(f"{name}: committed, but not a case")
-    for name, arrays in files.items():
-        target = FOLDER / f"{name}.npz"
-        problem = difference(arrays, load(target)) if target.exists() else "not committed"
-        print(f"{name}: {problem or f'{len(arrays)} arrays identical'}")
-        if problem:
-            failed.append(name)
-    return 1 if failed else 0
-
-
-if __name__ == "__main__":
-    sys.exit(main())
+        np.savez_compressed(folder / f"{name}.npz", **got)

@@ -7,11 +7,11 @@ Run in the build container (needs the reference checkout, see oracle/refshim.py)
 
 Without names: every fixture of RECORDERS.  A recorder is a function `name(out_dir)` of one of the oracle/golden_*.py
 modules; it runs the reference's own code, checks oracle/dsp.py against it where the oracle restates it, and writes
-`name.npz` into out_dir.  The stand-ins that the recorders put into sys.modules conflict with each other, so every module
+`name.npz` into out_dir, or, where one file would be too large, one file per case into out_dir/name/ (`files(name)`).  The stand-ins that the recorders put into sys.modules conflict with each other, so every module
 runs in a child process of its own (`--into`), all of them at once.  --check compares arrays, not file bytes (an .npz is a
 zip with time stamps): the same array names, and per array the same dtype, the same shape and equal values (NaNs equal NaNs);
-it prints one line per fixture and exits non-zero on any difference, on a recorder that fails, and on a committed fixture
-that no recorder writes.
+it prints one line per fixture (`name (K files): ...` for a folder of case files) and exits non-zero on any difference, on a
+recorder that fails, and on an .npz under tests/golden/, subfolders included, that no recorder writes.
 """
 from __future__ import annotations
 
@@ -36,6 +36,7 @@ RECORDERS = {       # module -> the fixtures it records
     "golden_levels": ("levels",),
     "golden_scope": ("scope",),
     "golden_plotcurves": ("plotcurves",),
+    "golden_spectrogrambatch": ("spectrogrambatch",),
     "golden_tables": ("filter_tables",),
 }
 
@@ -44,7 +45,15 @@ def files(name):
     """Where the files that recorder `name` writes are committed."""
     if name == "filter_tables":
         return [ROOT / "friture_amd" / "data" / "octave_filters.npz", GOLD / "filter_tables.sha256"]
+    if name == "spectrogrambatch":      # one file per case: together they would pass the size limit of a committed file
+        from .spectrogrambatch import GOLDEN_CASES, GOLDEN_FOLDER
+        return [GOLD / GOLDEN_FOLDER / f"{case}.npz" for case in GOLDEN_CASES]
     return [GOLD / f"{name}.npz"]
+
+
+def recorded(f, out_dir):
+    """Where the recorder leaves committed file f below its out_dir: by name, a file of a subfolder of tests/golden/ in that subfolder."""
+    return Path(out_dir) / (f.relative_to(GOLD) if GOLD in f.parents else f.name)
 
 
 def load(path):
@@ -91,7 +100,8 @@ def main():
 
     failed = []
     if not args.names:
-        failed = sorted({p.stem for p in GOLD.glob("*.npz")} - set(module_of))
+        owned = {f for name in module_of for f in files(name)}
+        failed = sorted(str(p.relative_to(GOLD).with_suffix("")) for p in GOLD.rglob("*.npz") if p not in owned)
         for name in failed:
             print(f"{name}: committed, but no recorder writes it")
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor() as pool:
@@ -99,7 +109,7 @@ def main():
             if child.returncode or not args.check:
                 print(child.stdout, end="")
             for name in mine:
-                pairs = [(Path(tmp) / f.name, f) for f in files(name)]
+                pairs = [(recorded(f, tmp), f) for f in files(name)]
                 problem = None
                 if child.returncode or not all(new.exists() for new, _ in pairs):
                     problem = f"recorder failed (exit status {child.returncode})"
@@ -110,7 +120,8 @@ def main():
                     for new, old in pairs:
                         shutil.copyfile(new, old)
                     done = "written to " + ", ".join(str(old.relative_to(ROOT)) for _, old in pairs)
-                print(f"{name}: {problem or done}")
+                label = name if pairs[0][1].parent.parent != GOLD else f"{name} ({len(pairs)} files)"      # a folder of case files
+                print(f"{label}: {problem or done}")
                 if problem:
                     failed.append(name)
     return 1 if failed else 0

@@ -1,4 +1,4 @@
-"""Shared by the SpectrogramBatch tests, tools/record_spectrogrambatch_golden.py and tools/bench_spectrogrambatch.py: the case list and the
+"""Shared by the SpectrogramBatch tests and their recorder (oracle/golden_spectrogrambatch.py): the case list and the
 spectrogram widget's body replayed chunk by chunk over oracle.dsp and plain numpy, in the reference's operation order
 (friture/spectrogram.py:131-173, signal/frequency_resampler.py:67-83, signal/online_linear_2D_resampler.py:57-97,
 signal/linear_interp.py:51-60, signal/color_tranform.py:48-51, signal/lookup_table.py:50-52).  Nothing here touches the GPU or the
@@ -9,8 +9,10 @@ from fractions import Fraction
 
 import numpy as np
 
-from oracle import dsp
-from oracle.cases import FS, chunk_ends
+from . import dsp
+from .cases import FS, chunk_ends, synth  # noqa: F401 (synth: the cases' input, for the tests and the recorder)
+
+GOLDEN_FOLDER = "spectrogrambatch"      # under tests/golden/: one file per case
 
 # The recorded cases (tests/golden/spectrogrambatch/<case>.npz).  `overlap` is a Fraction as in the widget (overlap_frac); the float the
 # widget divides with is float(overlap).
@@ -31,7 +33,7 @@ OVER_EMISSION = dict(fft_size=1000, overlap=Fraction(2, 3), screen_width=640, sc
 
 
 def load_golden(folder):
-    """{case: {array name: array}} of the recorded files."""
+    """{case: {array name: array}} of the recorded files in `folder` (tests/golden/spectrogrambatch)."""
     out = {}
     for name in GOLDEN_CASES:
         with np.load(folder / f"{name}.npz", allow_pickle=False) as z:
@@ -45,23 +47,6 @@ def case_ends(case):
     rng = np.random.default_rng(case["seed"])
     ends = np.cumsum(rng.choice([1, 100, 512, 512, 640, 3000], size=400))
     return np.concatenate([ends[ends < case["n"]], [case["n"]]]).astype(np.int64)
-
-
-def synth(kind, n, seed):
-    """tests/conftest.synth (seeded float32 PCM), here so that the recorder can use it without pytest."""
-    rng = np.random.default_rng(seed)
-    t = np.arange(n)
-    if kind == "noise":
-        x = 0.25 * rng.standard_normal(n)
-    elif kind == "tone":
-        x = 0.5 * np.sin(2 * np.pi * 1000.0 * t / 48000.0) + 1e-3 * rng.standard_normal(n)
-    elif kind == "chirp":
-        dur = n / 48000.0
-        k = np.log(20000.0 / 20.0) / dur
-        x = 0.5 * np.sin(2 * np.pi * 20.0 * (np.exp(k * t / 48000.0) - 1.0) / k)
-    else:
-        raise ValueError(kind)
-    return x.astype(np.float32)
 
 
 def settings(fft_size=4096, overlap=Fraction(3, 4), spec_min=-140., spec_max=0., weighting=0, scale="mel", minfreq=20., maxfreq=20000.,
@@ -150,24 +135,15 @@ def screen_replay(norm, frame_start, st, old=None, orig_index=0., resampled_inde
 
 
 def frames_replay(x, ends, st):
-    """The widget's frame loop: one stream x [T] float64 through MirrorRing -> psd_frame -> dB + weighting -> normalisation, chunk by
-    chunk.  Returns (norm [F, B], frame_start [R + 1], refresh_chunk [R])."""
-    x = np.asarray(x, np.float64)
-    N, hop, needed = st["fft_size"], st["hop"], st["needed"]
-    window = dsp.hann_symmetric(N)
-    biggest = int(np.max(np.diff(np.concatenate([[0], ends])))) if len(ends) else 0
-    ring, old_index, pos = dsp.MirrorRing(max(10000, 2 * (N + hop + biggest))), 0, 0
+    """The widget's frame loop (dsp.widget_frames): one stream x [T] float64 -> psd_frame -> dB + weighting -> normalisation, chunk
+    by chunk.  Returns (norm [F, B], frame_start [R + 1], refresh_chunk [R])."""
+    window = dsp.hann_symmetric(st["fft_size"])
     norm, frame_start, refresh_chunk = [], [0], []
-    for c, e in enumerate(ends):
-        ring.push(x[None, pos:e])
-        pos = int(e)
-        realizable = int(np.floor((ring.offset - old_index) / needed))
-        if realizable <= 0:
-            continue
+    for c, frames in dsp.widget_frames(np.asarray(x, np.float64)[None], ends, st["fft_size"], st["needed"]):
+        realizable = len(frames)
         spn = np.zeros((len(st["freq"]), realizable))
         for i in range(realizable):
-            spn[:, i] = dsp.psd_frame(ring.data_indexed(old_index, N)[0], window)
-            old_index += hop
+            spn[:, i] = dsp.psd_frame(frames[i, 0], window)
         w = np.tile(st["weight"][:, None], (1, realizable))
         norm.append(dsp.normalise(dsp.log_spectrum(spn) + w, st["spec_min"], st["spec_max"]).T)
         frame_start.append(frame_start[-1] + realizable)

@@ -59,33 +59,21 @@ def _collect(per_stream, refresh_chunk, freq):
 
 
 def replay(x, fft_size=8192, overlap=0.75, weighting=1, response_time=0.025, chunk=512, ends=None):
-    """x: [S, rows, T] float64 (rows 1, or 2 for dual channels).  Every stream through MirrorRing -> psd_frame ->
-    spectrum_readout chunk by chunk.  Returns dict(db [S, R, B], smoothed [S, R, rows, B], peak_index, pitch_index, fmax, fpitch
-    [S, R], refresh_chunk [R])."""
+    """x: [S, rows, T] float64 (rows 1, or 2 for dual channels).  Every stream through the widget's frame loop
+    (dsp.widget_frames) -> psd_frame -> spectrum_readout chunk by chunk.  Returns dict(db [S, R, B], smoothed [S, R, rows, B],
+    peak_index, pitch_index, fmax, fpitch [S, R], refresh_chunk [R])."""
     x = np.asarray(x, np.float64)
     S, rows, T = x.shape
-    hop, needed, alpha, kernel, weight, freq = settings(fft_size, overlap, weighting, response_time)
+    _, needed, alpha, kernel, weight, freq = settings(fft_size, overlap, weighting, response_time)
     ends = chunk_ends(T, chunk) if ends is None else np.asarray(ends, np.int64)
     window = dsp.hann_symmetric(fft_size)
-    biggest = int(np.max(np.diff(np.concatenate([[0], ends])))) if len(ends) else 0
     per_stream, refresh_chunk = [], []
     for s in range(S):
-        ring, old_index, pos = dsp.MirrorRing(max(10000, 2 * (fft_size + hop + biggest))), 0, 0      # loses nothing
         prev = np.zeros((rows, len(freq)))
         got, chunks = [], []
-        for c, e in enumerate(ends):
-            ring.push(x[s, :, pos:e])
-            pos = int(e)
-            realizable = int(np.floor((ring.offset - old_index) / needed))
-            if realizable <= 0:
-                continue
-            cols = [[] for _ in range(rows)]
-            for _ in range(realizable):
-                frame = ring.data_indexed(old_index, fft_size)
-                for r in range(rows):
-                    cols[r].append(dsp.psd_frame(frame[r], window))
-                old_index += hop
-            prev, last = readouts([np.stack(c_, axis=1) for c_ in cols], kernel, alpha, prev, weight, freq)
+        for c, frames in dsp.widget_frames(x[s], ends, fft_size, needed):
+            spn = [np.stack([dsp.psd_frame(f[r], window) for f in frames], axis=1) for r in range(rows)]
+            prev, last = readouts(spn, kernel, alpha, prev, weight, freq)
             got.append(dict(last, smoothed=prev))
             chunks.append(c)
         per_stream.append(got)

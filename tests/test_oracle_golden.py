@@ -194,16 +194,18 @@ def test_pitch_upstream_known_answers(golden):
 
 @pytest.mark.skipif(not refshim.available(), reason="needs the reference checkout (FRITURE_REFERENCE): the recorders execute it")
 def test_committed_fixtures_are_what_the_reference_records():
-    """python -m oracle.make_golden --check: every fixture under tests/golden/ and the filter tables, recorded again from the
-    unmodified reference, equal the committed files array for array (names, dtypes, shapes, values; no tolerance)."""
+    """python -m oracle.make_golden --check: every fixture under tests/golden/ (a subfolder's files are one fixture, named after
+    the folder) and the filter tables, recorded again from the unmodified reference, equal the committed files array for array
+    (names, dtypes, shapes, values; no tolerance)."""
     root = Path(__file__).resolve().parents[1]
     run = subprocess.run([sys.executable, "-m", "oracle.make_golden", "--check"], cwd=root, capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr
-    compared = {m[1]: int(m[2]) for m in re.finditer(r"^(\w+): (\d+) arrays identical$", run.stdout, re.M)}
-    want = {}
-    for p in (root / "tests" / "golden").glob("*.npz"):
+    compared = {m[1]: int(m[2]) for m in re.finditer(r"^(\w+)(?: \(\d+ files\))?: (\d+) arrays identical$", run.stdout, re.M)}
+    want, gold = {}, root / "tests" / "golden"
+    for p in gold.rglob("*.npz"):
+        name = p.stem if p.parent == gold else p.parent.relative_to(gold).as_posix()
         with np.load(p, allow_pickle=False) as z:
-            want[p.stem] = len(z.files)
+            want[name] = want.get(name, 0) + len(z.files)
     want["filter_tables"] = len((root / "tests" / "golden" / "filter_tables.sha256").read_text().splitlines())
-    assert len(want) >= 14 and all(want.values())
+    assert len(want) >= 15 and want["spectrogrambatch"] > 0 and all(want.values())
     assert compared == want, run.stdout

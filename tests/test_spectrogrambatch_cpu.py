@@ -1,5 +1,5 @@
 """SpectrogramBatch without a GPU: the numpy replay of the widget chain against tests/golden/spectrogrambatch/
-(recorded from the reference classes by tools/record_spectrogrambatch_golden.py), the frame schedule and the column table against
+(recorded from the reference classes by oracle/golden_spectrogrambatch.py), the frame schedule and the column table against
 the recorded tables, and the new entry point in the header, the ctypes table and the library."""
 from fractions import Fraction
 from pathlib import Path
@@ -7,11 +7,11 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import spectrogrambatch_helpers as H
+from conftest import synth
+from oracle import spectrogrambatch as H
 from oracle import spectrumbatch as SH
-from oracle import refshim
 from oracle.cases import chunk_ends
-from test_spectrumbatch_cpu import _ragged
+from oracle.cases import ragged_ends as _ragged
 from friture_amd.plotting import frequency_scales as fscales
 from friture_amd.spectrogram import SpectrogramBatch, SpectrogramState
 from friture_amd.spectrum import SpectrumBatch, SpectrumState
@@ -168,14 +168,11 @@ def test_golden_files_are_small():
     assert sorted(p.stem for p in GOLDEN.glob("*.npz")) == sorted(H.GOLDEN_CASES)
 
 
-@pytest.mark.skipif(not refshim.available(), reason="needs the reference checkout (FRITURE_REFERENCE): the recorder executes it")
-def test_committed_fixtures_are_what_the_reference_records():
-    """tools/record_spectrogrambatch_golden.py --check: the reference classes, run again, give the committed arrays exactly."""
-    import subprocess
-    import sys
-    root = Path(__file__).resolve().parents[1]
-    run = subprocess.run([sys.executable, str(root / "tools" / "record_spectrogrambatch_golden.py"), "--check"], cwd=root,
-                         capture_output=True, text=True)
-    assert run.returncode == 0, run.stdout + run.stderr
-    for name in H.GOLDEN_CASES:
-        assert f"{name}: 13 arrays identical" in run.stdout, run.stdout
+def test_the_oracle_synth_is_the_tests_synth():
+    """oracle.cases.synth (the recorders cannot import conftest) and conftest.synth give the same arrays."""
+    for kind in ("noise", "tone", "chirp"):
+        for n, seed in [(1, 1), (4800, 11), (12000, 12)]:
+            a, b = H.synth(kind, n, seed), synth(kind, n, seed)
+            assert a.dtype == b.dtype == np.float32 and a.shape == b.shape == (n,) and np.array_equal(a, b), (kind, n)
+    with pytest.raises(ValueError):
+        H.synth("square", 10, 0)

@@ -1,5 +1,5 @@
 """SpectrogramBatch on the GPU (specgrambatch.hip): the kernel on given frames against the numpy replay of the widget chain
-(spectrogrambatch_helpers, pinned to the reference by test_spectrogrambatch_cpu), the whole route against the replay and against
+(oracle.spectrogrambatch, pinned to the reference by test_spectrogrambatch_cpu), the whole route against the replay and against
 SpectrogramStream fed chunk by chunk, and its invariances."""
 import ctypes
 from fractions import Fraction
@@ -8,8 +8,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import spectrogrambatch_helpers as H
 from conftest import synth
+from oracle import spectrogrambatch as H
 from oracle.cases import chunk_ends
 
 pytestmark = pytest.mark.gpu

@@ -4,14 +4,8 @@ import numpy as np
 import pytest
 
 from oracle import spectrumbatch as H
+from oracle.cases import ragged_ends as _ragged
 from friture_amd.spectrum import SpectrumBatch, SpectrumState
-
-
-def _ragged(T, seed):
-    rng = np.random.default_rng(seed)
-    steps = rng.choice([1, 7, 100, 512, 512, 512, 640, 3000, 20000], size=400)
-    ends = np.cumsum(steps)
-    return np.concatenate([ends[ends < T], [T]]).astype(np.int64)
 
 
 def _check(sb, T, ends, pending):
