@@ -97,6 +97,10 @@ SIGNATURES = {
     "frt_pitch_set_scratch_limit": (c_int, [c_void_p, c_int64]),
     "frt_pitch_frames_for": (c_int64, [c_void_p, c_int64]),
     "frt_pitch_track": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
+    "frt_pitch_track_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64,
+                                     c_void_p, c_void_p, POINTER(c_int64)]),
+    "frt_pitch_refresh": (c_int, [c_void_p, c_int, c_int64, POINTER(c_int64), c_int64, c_void_p, c_int64, c_double, c_double, c_int,
+                                  c_void_p, c_void_p, c_void_p]),
     "frt_delay_create": (c_int, [POINTER(c_void_p), POINTER(c_double), POINTER(c_double), c_int, c_int]),
     "frt_delay_destroy": (None, [c_void_p]),
     "frt_delay_stream": (c_void_p, [c_void_p]),

@@ -21,6 +21,7 @@
 #include <limits>
 
 #include "common.h"
+#include "pitch_plan.h"
 
 namespace frt {
 
@@ -537,6 +538,18 @@ extern "C" int64_t frt_pitch_frames_for(const frt_pitch* h, int64_t T) {
 
 extern "C" int frt_pitch_track(frt_pitch* h, const double* x, int64_t T, int64_t x_stride, double* f0_out, double* raw_out,
                                int64_t* n_frames_out) {
+    return pitch_track_with_level(h, x, T, x_stride, f0_out, raw_out, n_frames_out, nullptr);
+}
+
+void frt::pitch_plan_shape(const frt_pitch* h, int* fft_size, int* hop, int* n_channels) {
+    *fft_size = h->N;
+    *hop = h->hop;
+    *n_channels = h->C;
+}
+
+// frt_pitch_track; with `level` (pitch_plan.h) the frame levels come from the caller instead of the rows of x
+int frt::pitch_track_with_level(frt_pitch* h, const double* x, int64_t T, int64_t x_stride, double* f0_out, double* raw_out,
+                                int64_t* n_frames_out, const PitchLevelSource* level) {
     FRT_REQUIRE(h, "frt_pitch_track: null handle");
     FRT_REQUIRE(T >= 0 && x_stride >= T, "frt_pitch_track: bad T/x_stride");
     const int64_t F = frt_pitch_frames_for(h, T);
@@ -593,7 +606,9 @@ extern "C" int frt_pitch_track(frt_pitch* h, const double* x, int64_t T, int64_t
             hipLaunchKernelGGL(pitch_loggrid_reg_kernel<32>, dim3(blocks * (kFramesPerBlock / kFramesPerGroup)), dim3(256), 0, h->stream, a);
         else
             hipLaunchKernelGGL(pitch_loggrid_kernel, dim3(blocks * (kFramesPerBlock / kFramesPerGroup)), dim3(256), 0, h->stream, a);
-        if (h->N % h->hop == 0 && h->N / h->hop >= 2) {
+        if (level) {
+            // filled once for all frames, below
+        } else if (h->N % h->hop == 0 && h->N / h->hop >= 2) {
             const int per_frame = h->N / h->hop;
             const long long n_blocks = fc + per_frame - 1;             // hop-sized blocks the chunk's frames cover
             if ((rc = h->eb.reserve((size_t)h->C * n_blocks * sizeof(double)))) return rc;
@@ -610,6 +625,7 @@ extern "C" int frt_pitch_track(frt_pitch* h, const double* x, int64_t T, int64_t
         FRT_HIP_CHECK(hipGetLastError());
         (void)groups;
     }
+    if (level && (rc = level->fill(level->ctx, a.raw + 2 * out_n, F, h->stream))) return rc;
     hipLaunchKernelGGL(pitch_gate_kernel, dim3(h->C), dim3(kGateThreads), 0, h->stream, a.raw, h->C, (long long)F, h->min_db,
                        h->conf, h->p_delta, h->prev.as<double>(), df0);
     FRT_HIP_CHECK(hipGetLastError());

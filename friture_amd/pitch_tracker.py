@@ -5,16 +5,19 @@ The tracker matches each frame's log-frequency spectrum against SWIPE-style harm
 table construction below (one-off, host side) produces the same numbers as the reference's loop over
 harmonics, the per-frame work — spectrum, log-grid interpolation, the [candidates x grid] product,
 peak refinement and the voiced/unvoiced gate — runs in the kernels of csrc/pitch.hip (frt_pitch_*).
-The Qt widget around it (PitchTrackerWidget, :57-158) is out of scope.
+The Qt widget around it (PitchTrackerWidget, :57-158) is out of scope, except for what it shows of whole
+recordings: `PitchBatch` (the refresh schedule, the latest estimate and the curve of handle_new_data / update_curve, :109-119).
 """
 from __future__ import annotations
 
 import ctypes
 import math
+from typing import NamedTuple
 
 import numpy as np
 
 from . import _lib
+from ._batchio import check_samples, chunk_ends, null_stream, source
 from .audioproc import audioproc
 from .constants import SAMPLING_RATE
 from .ringbuffer import RingBuffer
@@ -292,3 +295,184 @@ class PitchTracker:
 
     def get_latest_estimate(self) -> float:
         return self.out_buf.data_indexed(self.out_offset, 1)[0, 0]
+
+
+# ---- the widget's chain over whole recordings -----------------------------------------------------------------------------
+
+def pitch_schedule(n_samples, fft_size, step, chunk=512, ends=None, pending=0):
+    """(frame_start [R + 1], refresh_chunk [R]) of a stream of n_samples seen chunk by chunk by the pitch widget (update /
+    new_frames, pitch_tracker.py:313-332; handle_new_data, :109-112).  Frame g is the fft_size samples from g * step on, counted
+    from the first of the `pending` samples received and not consumed before this stream; it completes in the first chunk whose
+    end e has pending + e >= g * step + fft_size, and a chunk refreshes iff it completes at least one frame.  `ends`: the
+    chunks' end indices, for ragged chunks; default: the ends of `chunk`-sample chunks, a short last chunk is a short chunk."""
+    n_samples = int(n_samples)
+    if ends is None:
+        if chunk < 1:
+            raise ValueError(f"chunk {chunk}")
+        ends = chunk_ends(n_samples, chunk)
+    else:
+        ends = np.asarray(ends, np.int64).reshape(-1)
+        if ends.size and (ends[0] < 0 or ends[-1] > n_samples or np.any(np.diff(ends) < 0)):
+            raise ValueError(f"ends must be sorted and within [0, {n_samples}]")
+    have = ends + int(pending)
+    done = np.where(have >= fft_size, (have - fft_size) // step + 1, 0)          # frames complete after each chunk
+    fresh = np.diff(done, prepend=0) > 0
+    return np.concatenate([[0], done[fresh]]).astype(np.int64), np.flatnonzero(fresh).astype(np.int64)
+
+
+class PitchState(NamedTuple):
+    """What a pitch widget carries between two calls."""
+    tail: object            # [S, rows, pending] float64 (float32 input widened exactly): the samples from the next frame's first on
+    pending: int            # received and not consumed (below fft_size)
+    previous: object        # [S] float64: the gate's previous estimate, NaN = none
+    history: object         # [S, M] float64: the last M estimates (NaN = unvoiced), zeros before the first
+
+
+class PitchResult(NamedTuple):
+    estimates: object       # [S, F] float64, NaN = unvoiced; [F] for one stream given without its axis (likewise below)
+    raw: object             # [3, S, F] float64 (estimate before the gate, confidence, dBFS) with with_raw, else None
+    frame_start: object     # [R + 1] int64 (host): refresh r completes the frames frame_start[r] .. frame_start[r + 1] - 1
+    refresh_chunk: object   # [R] int64 (host): the chunk that caused each refresh
+    pitch: object           # [S, R] float64: the latest estimate at each refresh
+    curve: object           # [S, M] (keep="last": the curve after the last refresh) or [S, R, M] (keep="all"), within [0, 1]
+    times: object           # [M] float64 (host): linspace(0, 1, M)
+    state: PitchState
+
+
+class PitchBatch:
+    """S streams of a whole recording through the pitch tracker widget's chain in device calls, as widgets fed chunk by chunk
+    would have seen it: the kernels of PitchEngine on row 0 of every frame, the gate's level as the RMS over every row of the
+    frame (one row, or two with dual_channels: pitch_tracker.py:370, 404-407), the gate, and per refresh the latest estimate
+    and the curve of update_curve (:114-119: the last M = floor(duration / (step / sample_rate)) + 1 estimates on the OctaveC
+    axis between min_freq and max_freq, flipped and clipped; unvoiced estimates and the zeros before the first frame sit at 1).
+    Fixed settings, no pause.
+
+    run(x, chunk=512 | ends=..., state=None, keep="last" | "all", with_raw=False) takes [S, T] ([S, 2, T] with dual_channels;
+    the stream axis may be left out for one stream), float32 or float64, numpy array or CUDA tensor.  Results are numpy for numpy
+    input and CUDA tensors for CUDA input.  Spectra, grid spectra and strengths of the frames live in at most `scratch_bytes` of
+    device memory: longer recordings go through in slabs of frames, with the same bits whatever the slab size; the number of
+    launches and copies of a run depends on the number of slabs only, not on frames or refreshes.
+
+    The chain is defined on the true samples: what the reference shows as long as chunk + fft_size stays within the 10000
+    samples of its ring (ringbuffer.py:34), beyond which its frames read samples the ring has already overwritten.  For one
+    row, `estimates` equals PitchEngine.track on the same float64 samples, bit for bit, where track's rows start on 16-byte
+    boundaries (an even number of samples per row): the transform has another instance for rows that do not, which from fft_size
+    2048 on rounds differently (4e-16 relative in the estimates), and PitchBatch always uses the aligned one, so that a
+    recording cut at any sample gives the bits of the recording fed whole."""
+
+    def __init__(self, fft_size: int = DEFAULT_FFT_SIZE, overlap: float = 0.75, sample_rate: int = SAMPLING_RATE,
+                 min_freq: float = DEFAULT_MIN_FREQ, max_freq: float = DEFAULT_MAX_FREQ, min_db: float = DEFAULT_MIN_DB,
+                 cres: int = DEFAULT_C_RES, conf: float = DEFAULT_P_CONF, p_delta: int = DEFAULT_P_DELTA,
+                 duration: float = DEFAULT_DURATION, dual_channels: bool = False):
+        self.fft_size = int(fft_size)
+        self.overlap = overlap
+        self.sample_rate = sample_rate
+        self.min_freq, self.max_freq = min_freq, max_freq
+        self.min_db, self.cres, self.conf, self.p_delta = min_db, cres, conf, p_delta
+        self.duration = duration
+        self.dual_channels = bool(dual_channels)
+        self.rows = 2 if self.dual_channels else 1
+        self.step = math.floor(self.fft_size * (1.0 - overlap))
+        if self.step < 1:
+            raise ValueError(f"fft_size {fft_size} with overlap {overlap}: no frame advance")
+        if not 0 < min_freq < max_freq:
+            raise ValueError(f"axis range [{min_freq}, {max_freq}]")
+        self.n_history = math.floor(duration / (self.step / sample_rate)) + 1          # get_estimates, :325-327
+        if self.n_history < 1:
+            raise ValueError(f"duration {duration}")
+        self.times = np.linspace(0, 1.0, self.n_history)
+        self.grid, self.candidates, self.kernels = swipe_tables(sample_rate, min_freq, max_freq, cres)
+        self._engines = {}
+
+    # ---- host only ------------------------------------------------------------------------------------------------------------
+    def schedule(self, n_samples, chunk=512, ends=None, state=None):
+        """pitch_schedule for this widget's frame size and step, from a carried state's pending samples on."""
+        return pitch_schedule(n_samples, self.fft_size, self.step, chunk, ends, 0 if state is None else state.pending)
+
+    # ---- device ---------------------------------------------------------------------------------------------------------------
+    def _check_input(self, x, state):
+        x, is_np, squeeze, pending = check_samples("PitchBatch", x, state, self.dual_channels)
+        S, M = x.shape[0], self.n_history
+        if state is not None:
+            want = {"tail": (S, self.rows, pending), "previous": (S,), "history": (S, M)}
+            got = {name: tuple(getattr(state, name).shape) for name in want}
+            if not 0 <= pending < self.fft_size or got != want:
+                raise ValueError(f"state of another shape: {got} (want {want}), pending {pending} (below {self.fft_size})")
+        return x.reshape(S, self.rows, x.shape[-1]), is_np, squeeze, pending
+
+    def _engine(self, streams):
+        if streams not in self._engines:
+            self._engines[streams] = PitchEngine(self.fft_size, self.step, streams, self.sample_rate, self.grid, self.kernels,
+                                                 self.min_db, self.conf, self.p_delta)
+        return self._engines[streams]
+
+    def run(self, x, chunk=512, ends=None, state=None, keep="last", with_raw=False, scratch_bytes=1 << 30):
+        if keep not in ("all", "last"):
+            raise ValueError(f"keep={keep!r} ('all' or 'last')")
+        x, is_np, squeeze, pending = self._check_input(x, state)
+        frame_start, refresh_chunk = self.schedule(x.shape[-1], chunk, ends, state)
+        if ends is not None:                                         # the widgets were pushed ends[-1] samples
+            x = x[..., :int(np.asarray(ends).reshape(-1)[-1]) if np.size(ends) else 0]
+        import torch
+        lib = _lib.init()
+        S, rows, T, M = x.shape[0], self.rows, x.shape[-1], self.n_history
+        F, R, L = int(frame_start[-1]), len(refresh_chunk), pending + x.shape[-1]
+        f64, vp = torch.float64, ctypes.c_void_p
+
+        def carried(value, shape, fill):                             # a copy on the device: the caller's state is not modified
+            if state is None:
+                return torch.full(shape, fill, dtype=f64, device=dev)
+            return torch.as_tensor(value).to(device=dev, dtype=f64).reshape(shape).clone()
+
+        with null_stream(x, is_np) as dev:
+            xd, x_ptr, code, strides = source(torch.from_numpy(np.ascontiguousarray(x)).to(dev) if is_np else x, True)
+            tail = carried(None if state is None else state.tail, (S, rows, pending), 0.0)
+            eng = self._engine(S)
+            est = torch.empty((S, F), dtype=f64, device=dev)
+            raw = torch.empty((3, S, F), dtype=f64, device=dev) if with_raw else None
+            previous = carried(None if state is None else state.previous, (S,), math.nan)
+            if F:
+                # The transform picks its instance by the alignment of its rows (16-byte row starts: an even stride from an
+                # aligned address), and the instances round differently from fft_size 2048 on.  Row 0 is therefore always handed
+                # over aligned, whatever the length of this piece, so that a recording in pieces gives the bits of the whole.
+                even = L + (L & 1)
+                if pending == 0 and code == 1 and x_ptr % 16 == 0 and (S == 1 or strides[0] % 2 == 0):
+                    row0, row0_stride = xd[:, 0, :], strides[0] if S > 1 else even          # row 0 as it lies
+                else:
+                    row0, row0_stride = torch.empty((S, even), dtype=f64, device=dev), even
+                    row0[:, :pending] = tail[:, 0, :]
+                    row0[:, pending:L] = xd[:, 0, :]
+                    row0[:, L:] = 0.0                                # the pad: never part of a frame
+                eng.set_scratch_limit(scratch_bytes)
+                _lib.check(lib.frt_pitch_set_stream(eng._h, None))
+                _lib.check(lib.frt_pitch_set_previous(eng._h, vp(previous.data_ptr())))
+                _lib.check(lib.frt_pitch_track_rows(eng._h, vp(row0.data_ptr()), row0_stride, vp(x_ptr), code, rows, T, strides[0],
+                                                    strides[1], vp(tail.data_ptr()) if pending else None, pending,
+                                                    vp(est.data_ptr()), vp(raw.data_ptr()) if with_raw else None, None))
+                _lib.check(lib.frt_pitch_get_previous(eng._h, vp(previous.data_ptr())))
+            history_in = carried(None if state is None else state.history, (S, M), 0.0)
+            history = torch.empty((S, M), dtype=f64, device=dev)
+            pitch = torch.empty((S, R), dtype=f64, device=dev)
+            curve = torch.empty((S, 1 if keep == "last" else R, M), dtype=f64, device=dev)
+            if R or keep == "last":
+                _lib.check(lib.frt_pitch_refresh(vp(est.data_ptr()) if F else None, S, F,
+                                                 frame_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), R,
+                                                 vp(history_in.data_ptr()), M, float(self.min_freq), float(self.max_freq),
+                                                 int(keep == "last"), vp(history.data_ptr()), vp(pitch.data_ptr()),
+                                                 vp(curve.data_ptr())))
+            if not R:
+                history = history_in
+            if keep == "last":
+                curve = curve[:, 0]
+            # behind the last frame: samples F * step .. L of tail || x, widened
+            used = F * self.step
+            new_tail = torch.cat([tail[:, :, min(used, pending):], xd[:, :, max(used - pending, 0):].to(f64)], dim=2)
+            new_state = PitchState(new_tail, L - used, previous, history)
+            if is_np:
+                est, pitch, curve = est.cpu().numpy(), pitch.cpu().numpy(), curve.cpu().numpy()
+                raw = raw.cpu().numpy() if with_raw else None
+                new_state = PitchState(new_tail.cpu().numpy(), L - used, previous.cpu().numpy(), history.cpu().numpy())
+        if squeeze:
+            est, pitch, curve = est[0], pitch[0], curve[0]
+            raw = raw[:, 0] if with_raw else None
+        return PitchResult(est, raw, frame_start, refresh_chunk, pitch, curve, self.times, new_state)

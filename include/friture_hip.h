@@ -369,6 +369,31 @@ int64_t frt_pitch_frames_for(const frt_pitch* h, int64_t T);
 int frt_pitch_track(frt_pitch* h, const double* x, int64_t T, int64_t x_stride, double* f0_out, double* raw_out,
                     int64_t* n_frames_out);
 
+/* ---- P3: the pitch tracker widget's chain over whole recordings (PitchBatch) --------------------------------------------
+ * frt_pitch_track for streams of one or two rows behind a carried tail: estimate and confidence from row 0, the gate's level
+ * from EVERY row of the frame (pitch_tracker.py:404-407: the RMS of the [rows, N] frame), then the gate of frt_pitch_track on
+ * that level, with the handle's previous estimates.  The handle has one channel per stream.
+ *   row0: [streams][row0_stride] doubles, pending + T valid samples: row 0 of tail || x per stream
+ *   x: sample t of row `row` of stream s at x[s * ld_stream + row * ld_row + t], dtype 0 float32 / 1 float64 (widened exactly)
+ *   tail: [streams][rows][pending] doubles, the samples received before x that no frame has consumed (NULL when pending == 0)
+ * Frame g is samples [g * hop, g * hop + fft_size) of tail || x; n_frames = frames_for(pending + T).  f0_out, raw_out: as
+ * frt_pitch_track.  Every buffer is device memory; launched on the null stream (which the handle is left on), one
+ * synchronisation at the end. */
+int frt_pitch_track_rows(frt_pitch* h, const double* row0, int64_t row0_stride, const void* x, int dtype, int rows, int64_t T,
+                         int64_t ld_stream, int64_t ld_row, const double* tail, int64_t pending, double* f0_out, double* raw_out,
+                         int64_t* n_frames_out);
+/* What the widget shows at each refresh (PitchTrackerWidget.handle_new_data / update_curve, :109-119).  estimates:
+ * [streams][n_frames]; frame_start: [n_refresh + 1] HOST int64, increasing from 0 to n_frames: refresh r completes frames
+ * frame_start[r] .. frame_start[r + 1] - 1; history_in: [streams][history_length], the estimates before these (zeros before the
+ * first).  pitch_out[s][r] = estimates[s][frame_start[r + 1] - 1]; curve_out: [streams][R'][history_length] with R' = n_refresh, or
+ * 1 with keep_last (the final refresh; with n_refresh == 0 the history as it stands): the last history_length entries of history || estimates up to the refresh, as
+ * clip(1 - (log2(fmax(f, 1e-20)) - log2(min_freq)) / (log2(max_freq) - log2(min_freq)), 0, 1) (fmax ignores NaN: unvoiced = 1);
+ * history_out (not history_in): the last history_length entries after the call.  Device buffers, null stream, one
+ * synchronisation at the end. */
+int frt_pitch_refresh(const double* estimates, int streams, int64_t n_frames, const int64_t* frame_start, int64_t n_refresh,
+                      const double* history_in, int64_t history_length, double min_freq, double max_freq, int keep_last,
+                      double* history_out, double* pitch_out, double* curve_out);
+
 /* ---- L1: level meters and long-time levels (Levels_Widget, LongLevelWidget) -----------------------------
  * Per channel and per chunk (friture/levels.py:85-124, iec.py, ballistic_peak.py:21-66,
  * signal/exp_smoothing.py:40-56): value_max = max|y| (chunks of length > 0); old_max = value_max if

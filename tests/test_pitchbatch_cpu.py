@@ -1,0 +1,144 @@
+"""PitchBatch without a GPU: the refresh schedule against a literal chunk loop of new_frames(), the history length, the
+properties of the numpy replay (tests/pitchbatch_helpers.py) that the GPU tests lean on, and — where the reference checkout is
+present — that replay against the reference's own PitchTracker fed chunk by chunk, with one row and with two."""
+import numpy as np
+import pytest
+
+import pitchbatch_helpers as H
+from friture_amd._batchio import chunk_ends
+from friture_amd.pitch_tracker import PitchBatch, PitchState, pitch_schedule
+from oracle import refshim
+
+TOL_F0 = 1e-9                                        # tests/test_pitch_gpu.py
+
+
+def literal_schedule(fft_size, step, ends, pending=0):
+    """PitchTracker.new_frames (:326-332) and handle_new_data (:109-112) as they are written, on offsets alone: the stream
+    starts `pending` samples after the next frame's first sample."""
+    offset, next_in_offset = pending, 0
+    frame_start, refresh_chunk = [0], []
+    for c, e in enumerate(ends):
+        offset = pending + e
+        new = 0
+        while next_in_offset + fft_size <= offset:
+            new += 1
+            next_in_offset += step
+        if new:
+            frame_start.append(frame_start[-1] + new)
+            refresh_chunk.append(c)
+    return frame_start, refresh_chunk
+
+
+@pytest.mark.parametrize("fft_size,overlap", [(4096, 0.75), (2048, 0.5), (1024, 0.75), (1024, 0.3), (32, 0.5)])
+def test_schedule_equals_a_literal_chunk_loop(fft_size, overlap):
+    pb = PitchBatch(fft_size, overlap)
+    assert pb.step == int(np.floor(fft_size * (1.0 - overlap)))
+    T = 60000
+    for chunk in (512, 100, 5000):
+        fs, rc = pb.schedule(T, chunk)
+        want_fs, want_rc = literal_schedule(fft_size, pb.step, chunk_ends(T, chunk).tolist())
+        assert fs.dtype == np.int64 and rc.dtype == np.int64
+        assert fs.tolist() == want_fs and rc.tolist() == want_rc and len(rc) > 0
+        assert fs[-1] == (T - fft_size) // pb.step + 1
+    for seed in (1, 2):
+        ends = H.ragged(T, seed)
+        fs, rc = pb.schedule(T, ends=ends)
+        want_fs, want_rc = literal_schedule(fft_size, pb.step, ends.tolist())
+        assert fs.tolist() == want_fs and rc.tolist() == want_rc
+    for pending in (1, pb.step - 1, fft_size - 1):                   # carried in from an earlier call
+        state = PitchState(None, pending, None, None)
+        for ends in (chunk_ends(T, 512), H.ragged(T, 3 + pending)):
+            fs, rc = pb.schedule(T, ends=ends, state=state)
+            want_fs, want_rc = literal_schedule(fft_size, pb.step, ends.tolist(), pending)
+            assert fs.tolist() == want_fs and rc.tolist() == want_rc
+    short = pb.schedule(fft_size - 1)                                # no frame completes: no refresh
+    assert short[0].tolist() == [0] and short[1].size == 0
+    assert pb.schedule(0)[0].tolist() == [0] and pb.schedule(0)[1].size == 0
+    one = pb.schedule(T, ends=[T])                                   # the whole recording as one chunk: one refresh
+    assert one[0].tolist() == [0, (T - fft_size) // pb.step + 1] and one[1].tolist() == [0]
+
+
+def test_schedule_is_the_pieces_schedules_joined():
+    fft_size, step, T, a = 1024, 256, 20000, 5001
+    ends = np.unique(np.concatenate([chunk_ends(T, 512), [a]]))
+    fs, rc = pitch_schedule(T, fft_size, step, ends=ends)
+    e1, e2 = ends[ends <= a], ends[ends > a] - a
+    fs1, rc1 = pitch_schedule(a, fft_size, step, ends=e1)
+    pending = a - int(fs1[-1]) * step
+    fs2, rc2 = pitch_schedule(T - a, fft_size, step, ends=e2, pending=pending)
+    assert np.array_equal(np.concatenate([fs1, fs2[1:] + fs1[-1]]), fs)
+    assert np.array_equal(np.concatenate([rc1, rc2 + len(e1)]), rc)
+
+
+def test_settings_and_bad_arguments():
+    assert PitchBatch().n_history == 469 and PitchBatch().step == 1024
+    assert PitchBatch().times.shape == (469,) and PitchBatch().times[0] == 0 and PitchBatch().times[-1] == 1
+    assert PitchBatch(1024, 0.75, duration=0.1).n_history == 19
+    with pytest.raises(ValueError):
+        PitchBatch(1024, 1.0)                                        # no frame advance
+    with pytest.raises(ValueError):
+        PitchBatch().schedule(100, ends=[50, 20])
+    with pytest.raises(ValueError):
+        PitchBatch().schedule(100, ends=[50, 200])
+    with pytest.raises(ValueError):
+        PitchBatch().schedule(100, chunk=0)
+
+
+def test_replay_curve_has_no_nan_and_is_one_for_unvoiced_and_for_the_zeros_before_the_first_frame():
+    y = H.axis_curve(np.array([np.nan, 0.0, 65.0, 1047.0, 20.0, 5000.0, 261.0]))
+    assert not np.any(np.isnan(y))
+    assert y[0] == 1.0 and y[1] == 1.0 and y[2] == 1.0 and y[3] == 0.0 and y[4] == 1.0 and y[5] == 0.0 and 0.0 < y[6] < 1.0
+    x = H.tone(1024 + 256 * 9, 220.0, -20.0, 1)
+    x[1024 + 256 * 4:] = 0.0                                          # the later frames fall silent: unvoiced
+    r = H.replay(x, chunk_ends(len(x), 512), fft_size=1024, overlap=0.75, duration=0.1)
+    assert r["n_history"] == 19 and r["curves"].shape == (len(r["refresh_chunk"]), 19)
+    assert not np.any(np.isnan(r["curves"]))
+    assert np.all(r["last_curve"][:19 - 10] == 1.0)                  # the ring's zeros
+    assert np.array_equal(r["last_curve"][19 - 10:] == 1.0, np.isnan(r["estimates"]))
+    assert np.isnan(r["estimates"][-1]) and not np.isnan(r["estimates"][0])
+    assert np.array_equal(r["pitch"], r["estimates"][r["frame_start"][1:] - 1], equal_nan=True)
+
+
+@pytest.mark.parametrize("fft_size,overlap", [(1024, 0.75), (2048, 0.5)])
+def test_dual_inputs_sit_a_decibel_away_from_the_threshold_on_opposite_sides(fft_size, overlap):
+    x = H.dual_inputs(fft_size * 12)
+    one, two = (H.replay(x[i], chunk_ends(x.shape[-1], 512), fft_size=fft_size, overlap=overlap) for i in range(2))
+    assert len(one["estimates"]) > 20
+    assert np.all(one["raw"][2] >= -50.0 + 1.0) and np.all(one["row0_db"] <= -50.0 - 1.0)
+    assert np.all(two["raw"][2] <= -50.0 - 1.0) and np.all(two["row0_db"] >= -50.0 + 1.0)
+    assert not np.any(np.isnan(one["estimates"])) and np.all(np.abs(one["estimates"] - 220.0) < 2.0)
+    assert np.all(np.isnan(two["estimates"])) and np.all(two["raw"][1] >= 0.5)       # unvoiced by the level alone
+
+
+@pytest.mark.skipif(not refshim.available(), reason="needs the reference checkout")
+@pytest.mark.parametrize("rows", [1, 2])
+def test_replay_equals_the_reference_tracker_fed_chunk_by_chunk(golden, rows):
+    from oracle.golden_pitch import import_reference_pitch_tracker
+    pt = import_reference_pitch_tracker()
+    from friture.ringbuffer import RingBuffer
+    g = golden("pitch")
+    fft_size, overlap, duration = 1024, 0.75, 0.1
+    cases = {name: g[f"N1024_{name}_x"].astype(np.float64) for name in ("steady220", "jump", "quiet")}
+    if rows == 2:
+        n = len(cases["jump"])
+        cases = {"jump": np.stack([cases["jump"], H.tone(n, 330.0, -30.0, 21)]), "one": H.dual_inputs(n)[0], "two": H.dual_inputs(n)[1]}
+    for name, x in cases.items():
+        x = np.atleast_2d(x)
+        for ends in (chunk_ends(x.shape[1], 512), H.ragged(x.shape[1], 5, largest=2500)):
+            ring = RingBuffer()
+            tracker = pt.PitchTracker(ring, fft_size=fft_size, overlap=overlap)
+            mine = H.WidgetReplay(fft_size=fft_size, overlap=overlap, duration=duration)
+            start, estimates = 0, []
+            for e in ends.tolist():
+                ring.push(x[:, start:e], 0.)
+                fresh = tracker.update()
+                assert mine.push(x[:, start:e]) == fresh, (name, e)
+                window = tracker.get_estimates(duration)
+                assert H.close(mine.get_estimates(), window, TOL_F0), (name, e)
+                if fresh:
+                    latest = tracker.get_latest_estimate()
+                    assert H.close(mine.pitch[-1], latest, TOL_F0)
+                    estimates.append(window[len(window) - (mine.frame_start[-1] - mine.frame_start[-2]):])
+                start = e
+            assert H.close(np.array(mine.estimates), np.concatenate(estimates), TOL_F0), name
+            assert len(mine.estimates) == (x.shape[1] - fft_size) // mine.step + 1
