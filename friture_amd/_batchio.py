@@ -1,4 +1,4 @@
-"""What the batch classes (LevelsBatch, ScopeBatch, CurveBatch, SpectrumBatch, SpectrogramBatch) share: their input is a float32/float64 numpy
+"""What the batch classes (LevelsBatch, ScopeBatch, CurveBatch, SpectrumBatch, SpectrogramBatch, PitchBatch, OctaveSpectrumBatch) share: their input is a float32/float64 numpy
 array or CUDA tensor, their results are of the same kind, and a recording is seen in chunks; for the two STFT chains, the sample
 front of run() (RecordingFront)."""
 from __future__ import annotations

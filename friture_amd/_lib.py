@@ -62,6 +62,11 @@ SIGNATURES = {
     "frt_octbank_set_state": (c_int, [c_void_p, POINTER(c_double)]),
     "frt_octbank_energies": (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(c_double), POINTER(c_double), c_int,
                                      c_void_p]),
+    "frt_octbank_tails_length": (c_int64, [c_void_p]),
+    "frt_octbank_get_tails": (c_int, [c_void_p, c_void_p]),
+    "frt_octbank_set_tails": (c_int, [c_void_p, c_void_p]),
+    "frt_octspec_run": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, POINTER(c_int64), c_int64, POINTER(c_double),
+                                POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, POINTER(c_int)]),
     "frt_decimate_multiple": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, POINTER(c_int)]),
     "frt_decimate_multiple_state": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int), c_void_p]),
     "frt_gcc_create": (c_int, [POINTER(c_void_p), c_int, c_int]),

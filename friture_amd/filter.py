@@ -161,6 +161,35 @@ class FirBank(IirBank):
 
     get_state = set_state
 
+    def set_tails(self, tails):
+        """The pending tails [n_channels, 9, bpo + 1, 511] float64 (per stage the band filters, then the decimator), numpy array or
+        CUDA tensor (frt_octbank_set_tails): the bank continues as the one they were read from."""
+        shape = (self.n_channels, NOCTAVE, self.bpo + 1, 511)
+        if isinstance(tails, np.ndarray) or not hasattr(tails, "data_ptr"):
+            tails = np.ascontiguousarray(tails, np.float64)
+            address = tails.ctypes.data
+        else:
+            import torch
+            assert tails.is_cuda and tails.dtype == torch.float64
+            tails = tails.contiguous()
+            address = tails.data_ptr()
+        if tuple(tails.shape) != shape:
+            raise ValueError(f"tails of shape {tuple(tails.shape)}, want {shape}")
+        _lib.check(self._lib.frt_octbank_set_tails(self._h, ctypes.c_void_p(address)))
+
+    def get_tails(self, out=None):
+        """The pending tails as set_tails takes them: a new numpy array, or written to the CUDA tensor `out`."""
+        shape = (self.n_channels, NOCTAVE, self.bpo + 1, 511)
+        if out is None:
+            out = np.empty(shape, np.float64)
+            address = out.ctypes.data
+        else:
+            import torch
+            assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == shape
+            address = out.data_ptr()
+        _lib.check(self._lib.frt_octbank_get_tails(self._h, ctypes.c_void_p(address)))
+        return out
+
 
 def _bank_for(blow, alow, forward, feedback):
     key = (np.asarray(blow, np.float64).tobytes(), np.asarray(alow, np.float64).tobytes(),

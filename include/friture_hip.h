@@ -181,6 +181,33 @@ int frt_octbank_set_state(frt_octbank* h, const double* z);
  * (weight_db may be NULL) instead of sp.  The band signals themselves are not written.  Mode 1: block <= 1024. */
 int frt_octbank_energies(frt_octbank* h, const float* x, int64_t n, int block, const double* alphas,
                          const double* weight_db, int as_db, float* energy_out);
+/* The pending tails of a mode-1 handle — the FFT bank's whole carried state (friture/filter.py:213-245) — read and set.
+ * tails: [n_channels][9][bands_per_octave + 1][511] doubles: per channel, per octave stage j = 0 (full rate) .. 8, per filter
+ * of the stage (the band-passes i = 0..bpo-1 as in boct_fir, then the decimator), the 511 outputs still to be added to the
+ * stage's next samples.  frt_octbank_tails_length: doubles per channel (0 for a mode-0 handle).  Host pointers (the call
+ * returns with the copy done) or device pointers (enqueued on the handle's stream).  frt_octbank_get_state / _set_state
+ * remain the exact IIR bank's. */
+int64_t frt_octbank_tails_length(const frt_octbank* h);
+int frt_octbank_get_tails(frt_octbank* h, double* tails);
+int frt_octbank_set_tails(frt_octbank* h, const double* tails);
+/* The octave-spectrum widget's chain over a recording (OctaveSpectrum_Widget.handle_new_data, friture/octavespectrum.py:91-122)
+ * as widgets fed chunk by chunk would have seen it; mode-1 handle, float64 results.  x: DEVICE samples [n_channels] rows of n
+ * samples x_stride elements apart, float32 (dtype 0) or float64 (dtype 1), n < 2^31.  ends: [n_refresh] HOST int64, the sample
+ * counts at which the widgets refresh, counted from x[0]: increasing, every chunk (ends[r] - ends[r-1], ends[0]) a multiple of
+ * 256 in [256, 1024], ends[n_refresh-1] <= n — 256 = 2^8 keeps the per-chunk decimation y[:N:2] of all nine stages on one grid,
+ * 1024 is where the reference's first-stage rfft(x, 1536) would start to crop.  Samples behind the last end are not consumed.
+ * alphas, weight_db (may be NULL): [9*bpo] HOST doubles.  energies_in / energies_out: [n_channels][9*bpo] DEVICE doubles, the
+ * smoothed energies sp before and after (two different buffers); the filters' state is the handle's tails (above), read and
+ * left behind.  Per refresh r and band: sp after the chunk by sp = E_b + sp (1 - alpha)^(256 / dec) over the chunk's 256-sample
+ * sub-blocks b, E_b the sub-block's zero-state energy alpha sum_i (1 - alpha)^(m-1-i) y_i^2 — the chunk's own
+ * exp_smoothed_value (friture/signal/exp_smoothing.py:40-56) to rounding.  db_out: [n_channels][R'][9*bpo] DEVICE doubles,
+ * 10 log10(sp + 1e-30) + weight_db, R' = n_refresh or 1 with keep_last (the final refresh); energy_out: sp itself in the same
+ * shape, or NULL.  The recording is walked in time slabs of whole refreshes whose scratch (staged samples, stage signals,
+ * block energies) stays within scratch_bytes (<= 0: one slab; a refresh at least); n_slabs_out (may be NULL) receives their
+ * number.  Launches and copies per call depend on the number of slabs only.  Enqueued on the handle's stream. */
+int frt_octspec_run(frt_octbank* h, const void* x, int dtype, int64_t n, int64_t x_stride, const int64_t* ends, int64_t n_refresh,
+                    const double* alphas, const double* weight_db, const double* energies_in, double* energies_out,
+                    double* db_out, double* energy_out, int keep_last, int64_t scratch_bytes, int* n_slabs_out);
 /* decimate_multiple (friture/signal/decimate.py:45-71) with carried state: n_stages chained
  * decimations by 2 of x [n_channels][n] -> out [n_channels][*n_out].  Needs a bands_per_octave = 0 handle. */
 int frt_decimate_multiple(frt_octbank* h, int n_stages, const double* x, int n, double* out, int* n_out);
