@@ -1,6 +1,8 @@
-"""What the batch classes (LevelsBatch, ScopeBatch, CurveBatch, SpectrumBatch, SpectrogramBatch, PitchBatch, OctaveSpectrumBatch) share: their input is a float32/float64 numpy
-array or CUDA tensor, their results are of the same kind, and a recording is seen in chunks; for the two STFT chains, the sample
-front of run() (RecordingFront)."""
+"""What the batch classes (LevelsBatch, ScopeBatch, CurveBatch, SpectrumBatch, SpectrogramBatch, PitchBatch, OctaveSpectrumBatch)
+share: their input is a float32/float64 numpy array or CUDA tensor, their results are of the same kind, and a recording is seen
+in chunks (chunk_ends, checked_ends, frame_schedule); for the four chains over recordings, the host side of run(): the input
+checks (check_keep, check_samples), the hand-over to the null stream, the device copy of a carried state (carried) and the way
+back to numpy (to_host); for the two STFT chains, the sample front (RecordingFront)."""
 from __future__ import annotations
 
 import ctypes
@@ -17,23 +19,27 @@ def chunk_ends(T, chunk=512):
     return np.minimum(np.arange(1, -(-T // chunk) + 1, dtype=np.int64) * chunk, T)
 
 
+def checked_ends(n_samples, chunk=512, ends=None):
+    """The chunks' end indices as an int64 vector: `ends`, sorted and within [0, n_samples], or the ends of `chunk`-sample chunks."""
+    n_samples = int(n_samples)
+    if ends is None:
+        if chunk < 1:
+            raise ValueError(f"chunk {chunk}")
+        return chunk_ends(n_samples, chunk)
+    ends = np.asarray(ends, np.int64).reshape(-1)
+    if ends.size and (ends[0] < 0 or ends[-1] > n_samples or np.any(np.diff(ends) < 0)):
+        raise ValueError(f"ends must be sorted and within [0, {n_samples}]")
+    return ends
+
+
 def frame_schedule(n_samples, needed, hop, chunk=512, ends=None, pending=0):
     """(frame_start [R + 1], refresh_chunk [R]) of a stream of n_samples seen chunk by chunk by a widget that transforms
     realizable = floor(available / needed) frames per chunk and advances by hop = int(needed) per frame (friture/spectrum.py:
     133-155, friture/spectrogram.py:131-160); `pending`: samples received and not consumed before the first one.  `ends`: the
     chunks' end indices, for ragged chunks; default: the ends of `chunk`-sample chunks, a short last chunk is a short chunk."""
-    n_samples = int(n_samples)
-    if ends is None:
-        if chunk < 1:
-            raise ValueError(f"chunk {chunk}")
-        ends = chunk_ends(n_samples, chunk)
-    else:
-        ends = np.asarray(ends, np.int64).reshape(-1)
-        if ends.size and (ends[0] < 0 or ends[-1] > n_samples or np.any(np.diff(ends) < 0)):
-            raise ValueError(f"ends must be sorted and within [0, {n_samples}]")
     old_index = -int(pending)
     frame_start, refresh_chunk = [0], []
-    for c, e in enumerate(ends.tolist()):
+    for c, e in enumerate(checked_ends(n_samples, chunk, ends).tolist()):
         realizable = int(np.floor((e - old_index) / needed))
         if realizable > 0:
             frame_start.append(frame_start[-1] + realizable)
@@ -74,7 +80,12 @@ def alloc(like, shape, dtype=np.float64, zero=False):
     return getattr(torch, name)(shape, dtype=getattr(torch, np.dtype(dtype).name), device=like.device)
 
 
-# ---- the sample front of SpectrumBatch.run and SpectrogramBatch.run --------------------------------------------------------------
+# ---- the host side of run() of the chains over recordings ----------------------------------------------------------------------
+
+def check_keep(keep, *allowed):
+    if keep not in allowed:
+        raise ValueError(f"keep={keep!r} ({' or '.join(repr(a) for a in allowed)})")
+
 
 def check_samples(who, x, state, dual=False):
     """(x with its stream axis, is_np, squeeze, pending) of a recording x [S, T] ([S, 2, T] with `dual`; the stream axis may be
@@ -110,6 +121,26 @@ def null_stream(x, is_np):
         null.synchronize()
 
 
+def carried(dev, value, shape, fill=0.0, copy=True):
+    """A float64 copy on `dev` of an array that a state carries: what run() writes to must not be the caller's state.  None, a
+    fresh widget: `fill`.  copy=False is for RecordingFront's tail alone, which is only read: a contiguous CUDA float64 tail is
+    then taken as it is, as it always was, and a call with a carried state is spared one device copy of [C, fft_size + pending]."""
+    import torch
+    if value is None:
+        return torch.full(shape, fill, dtype=torch.float64, device=dev) if fill else torch.zeros(shape, dtype=torch.float64, device=dev)
+    value = torch.as_tensor(value).to(device=dev, dtype=torch.float64).reshape(shape)
+    return value.clone() if copy else value.contiguous()
+
+
+def to_host(value):
+    """`value` with its tensors as numpy arrays: a (named) tuple field by field, anything else as it is.  EVERY tensor field
+    comes to the host: a state that is to keep a field on the device for numpy input must not go through here whole."""
+    if isinstance(value, tuple):
+        fields = [to_host(v) for v in value]
+        return type(value)(*fields) if hasattr(value, "_fields") else tuple(fields)
+    return value.cpu().numpy() if hasattr(value, "cpu") else value
+
+
 class RecordingFront:
     """The samples of a recording x [S, (rows,) T] behind a carried tail, as C = S * rows device rows, and the frames of a
     schedule transformed from them slab by slab.  To be made and used inside null_stream: making it stages x, load_tail the
@@ -126,11 +157,8 @@ class RecordingFront:
             self.x = self.x.contiguous()
 
     def load_tail(self, tail):
-        """The carried tail (None: zeros), copied: the caller's state is not modified."""
-        if tail is None:
-            self.tail = self.torch.zeros((self.C, self.L), dtype=self.torch.float64, device=self.dev)
-        else:
-            self.tail = self.torch.as_tensor(tail).to(device=self.dev, dtype=self.torch.float64).reshape(self.C, self.L).contiguous()
+        """The carried tail (None: zeros); it is only read."""
+        self.tail = carried(self.dev, tail, (self.C, self.L), copy=False)
 
     def window(self, a, b):
         """Samples [a, b) of tail || x per row as float64 (float32 widens exactly), unit stride along time."""

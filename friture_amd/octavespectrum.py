@@ -12,7 +12,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _lib
-from ._batchio import check_samples, null_stream, source
+from ._batchio import carried, check_keep, check_samples, null_stream, source, to_host
 from .constants import NOCTAVE, SAMPLING_RATE
 from .octavefilters import Octave_Filters
 from .signal.exp_smoothing import exp_smoothed_value_groups
@@ -207,8 +207,7 @@ class OctaveSpectrumBatch:
         return x, is_np, squeeze, pending
 
     def run(self, x, chunk=512, ends=None, state=None, keep="all", with_energy=False, scratch_bytes=1 << 30):
-        if keep not in ("all", "last"):
-            raise ValueError(f"keep={keep!r} ('all' or 'last')")
+        check_keep(keep, "all", "last")
         x, is_np, squeeze, pending = self._check_input(x, state)
         ends = self.schedule(x.shape[-1], chunk, ends, state)
         import torch
@@ -216,16 +215,10 @@ class OctaveSpectrumBatch:
         S, T, B, R = x.shape[0], x.shape[-1], self.nbands, len(ends)
         f64, vp = torch.float64, ctypes.c_void_p
         last = int(ends[-1]) if R else -pending                      # the consumed samples end here
-
-        def carried(value, shape):                                   # a copy on the device: the caller's state is not modified
-            if state is None:
-                return torch.zeros(shape, dtype=f64, device=dev)
-            return torch.as_tensor(value).to(device=dev, dtype=f64).reshape(shape).clone()
-
+        held, sp_in, tails_in = (None, None, None) if state is None else (state.samples, state.energies, state.tails)
         with null_stream(x, is_np) as dev:
             x0 = xd = torch.from_numpy(np.ascontiguousarray(x)).to(dev) if is_np else x
-            held = carried(None if state is None else state.samples, (S, pending))
-            sp_in = carried(None if state is None else state.energies, (S, B))
+            held, sp_in = carried(dev, held, (S, pending)), carried(dev, sp_in, (S, B))
             Ro = R if keep == "all" else min(R, 1)
             db = torch.empty((S, Ro, B), dtype=f64, device=dev)
             energy = torch.empty((S, Ro, B), dtype=f64, device=dev) if with_energy else None
@@ -236,7 +229,7 @@ class OctaveSpectrumBatch:
                 if state is None:
                     bank.reset()
                 else:
-                    bank.set_tails(carried(state.tails, (S, NOCTAVE, self.bandsperoctave + 1, 511)))
+                    bank.set_tails(carried(dev, tails_in, (S, NOCTAVE, self.bandsperoctave + 1, 511)))
                 if pending:                                          # the pending samples stand in front: one float64 buffer
                     xd = torch.cat([held, xd[:, :max(last, 0)].to(f64)], dim=1)[:, :pending + last]
                 xd, x_ptr, code, strides = source(xd, True)
@@ -256,14 +249,11 @@ class OctaveSpectrumBatch:
                     rest = torch.cat([held[:, pending + last:], rest], dim=1)
                 new_state = OctaveSpectrumState(sp_out, tails, rest.clone(memory_format=torch.contiguous_format), 0)
             else:
-                tails = carried(None if state is None else state.tails, (S, NOCTAVE, self.bandsperoctave + 1, 511))
+                tails = carried(dev, tails_in, (S, NOCTAVE, self.bandsperoctave + 1, 511))
                 new_state = OctaveSpectrumState(sp_in, tails, torch.cat([held, xd.to(f64)], dim=1), 0)
             new_state = new_state._replace(pending=int(new_state.samples.shape[1]))
             if is_np:
-                db = db.cpu().numpy()
-                energy = energy.cpu().numpy() if with_energy else None
-                new_state = OctaveSpectrumState(new_state.energies.cpu().numpy(), new_state.tails.cpu().numpy(),
-                                                new_state.samples.cpu().numpy(), new_state.pending)
+                db, energy, new_state = to_host((db, energy, new_state))
         if squeeze:
             db = db[0]
             energy = energy[0] if with_energy else None

@@ -17,7 +17,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _lib
-from ._batchio import check_samples, chunk_ends, null_stream, source
+from ._batchio import carried, check_keep, check_samples, checked_ends, null_stream, source, to_host
 from .audioproc import audioproc
 from .constants import SAMPLING_RATE
 from .ringbuffer import RingBuffer
@@ -305,16 +305,7 @@ def pitch_schedule(n_samples, fft_size, step, chunk=512, ends=None, pending=0):
     from the first of the `pending` samples received and not consumed before this stream; it completes in the first chunk whose
     end e has pending + e >= g * step + fft_size, and a chunk refreshes iff it completes at least one frame.  `ends`: the
     chunks' end indices, for ragged chunks; default: the ends of `chunk`-sample chunks, a short last chunk is a short chunk."""
-    n_samples = int(n_samples)
-    if ends is None:
-        if chunk < 1:
-            raise ValueError(f"chunk {chunk}")
-        ends = chunk_ends(n_samples, chunk)
-    else:
-        ends = np.asarray(ends, np.int64).reshape(-1)
-        if ends.size and (ends[0] < 0 or ends[-1] > n_samples or np.any(np.diff(ends) < 0)):
-            raise ValueError(f"ends must be sorted and within [0, {n_samples}]")
-    have = ends + int(pending)
+    have = checked_ends(n_samples, chunk, ends) + int(pending)
     done = np.where(have >= fft_size, (have - fft_size) // step + 1, 0)          # frames complete after each chunk
     fresh = np.diff(done, prepend=0) > 0
     return np.concatenate([[0], done[fresh]]).astype(np.int64), np.flatnonzero(fresh).astype(np.int64)
@@ -407,8 +398,7 @@ class PitchBatch:
         return self._engines[streams]
 
     def run(self, x, chunk=512, ends=None, state=None, keep="last", with_raw=False, scratch_bytes=1 << 30):
-        if keep not in ("all", "last"):
-            raise ValueError(f"keep={keep!r} ('all' or 'last')")
+        check_keep(keep, "all", "last")
         x, is_np, squeeze, pending = self._check_input(x, state)
         frame_start, refresh_chunk = self.schedule(x.shape[-1], chunk, ends, state)
         if ends is not None:                                         # the widgets were pushed ends[-1] samples
@@ -418,19 +408,14 @@ class PitchBatch:
         S, rows, T, M = x.shape[0], self.rows, x.shape[-1], self.n_history
         F, R, L = int(frame_start[-1]), len(refresh_chunk), pending + x.shape[-1]
         f64, vp = torch.float64, ctypes.c_void_p
-
-        def carried(value, shape, fill):                             # a copy on the device: the caller's state is not modified
-            if state is None:
-                return torch.full(shape, fill, dtype=f64, device=dev)
-            return torch.as_tensor(value).to(device=dev, dtype=f64).reshape(shape).clone()
-
+        tail, previous, history = (None, None, None) if state is None else (state.tail, state.previous, state.history)
         with null_stream(x, is_np) as dev:
             xd, x_ptr, code, strides = source(torch.from_numpy(np.ascontiguousarray(x)).to(dev) if is_np else x, True)
-            tail = carried(None if state is None else state.tail, (S, rows, pending), 0.0)
+            tail = carried(dev, tail, (S, rows, pending))
             eng = self._engine(S)
             est = torch.empty((S, F), dtype=f64, device=dev)
             raw = torch.empty((3, S, F), dtype=f64, device=dev) if with_raw else None
-            previous = carried(None if state is None else state.previous, (S,), math.nan)
+            previous = carried(dev, previous, (S,), math.nan)
             if F:
                 # The transform picks its instance by the alignment of its rows (16-byte row starts: an even stride from an
                 # aligned address), and the instances round differently from fft_size 2048 on.  Row 0 is therefore always handed
@@ -450,7 +435,7 @@ class PitchBatch:
                                                     strides[1], vp(tail.data_ptr()) if pending else None, pending,
                                                     vp(est.data_ptr()), vp(raw.data_ptr()) if with_raw else None, None))
                 _lib.check(lib.frt_pitch_get_previous(eng._h, vp(previous.data_ptr())))
-            history_in = carried(None if state is None else state.history, (S, M), 0.0)
+            history_in = carried(dev, history, (S, M))
             history = torch.empty((S, M), dtype=f64, device=dev)
             pitch = torch.empty((S, R), dtype=f64, device=dev)
             curve = torch.empty((S, 1 if keep == "last" else R, M), dtype=f64, device=dev)
@@ -469,9 +454,7 @@ class PitchBatch:
             new_tail = torch.cat([tail[:, :, min(used, pending):], xd[:, :, max(used - pending, 0):].to(f64)], dim=2)
             new_state = PitchState(new_tail, L - used, previous, history)
             if is_np:
-                est, pitch, curve = est.cpu().numpy(), pitch.cpu().numpy(), curve.cpu().numpy()
-                raw = raw.cpu().numpy() if with_raw else None
-                new_state = PitchState(new_tail.cpu().numpy(), L - used, previous.cpu().numpy(), history.cpu().numpy())
+                est, raw, pitch, curve, new_state = to_host((est, raw, pitch, curve, new_state))
         if squeeze:
             est, pitch, curve = est[0], pitch[0], curve[0]
             raw = raw[:, 0] if with_raw else None

@@ -11,7 +11,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from ._batchio import RecordingFront, check_samples, frame_schedule, null_stream
+from ._batchio import RecordingFront, carried, check_keep, check_samples, frame_schedule, null_stream, to_host
 from .audioproc import audioproc
 from .constants import SAMPLING_RATE
 from .plotting import frequency_scales as fscales
@@ -303,8 +303,7 @@ class SpectrogramBatch:
         return x, is_np, squeeze, pending
 
     def run(self, x, chunk=512, ends=None, state=None, keep="all", scratch_bytes=1 << 30):
-        if keep not in ("all", "screen"):
-            raise ValueError(f"keep={keep!r} ('all' or 'screen')")
+        check_keep(keep, "all", "screen")
         x, is_np, squeeze, pending = self._check_input(x, state)
         S, T = x.shape
         frame_start, refresh_chunk = self.schedule(T, chunk, ends, state)
@@ -322,14 +321,11 @@ class SpectrogramBatch:
         Po = P - c_lo
         col_start = np.searchsorted(table.column_refresh, np.arange(R + 1))          # the columns of each refresh
         src = np.where(table.filler, -1, table.src)
-        f64, vp = torch.float64, ctypes.c_void_p
+        vp = ctypes.c_void_p
         with null_stream(x, is_np) as dev:
             front = RecordingFront(x, is_np, dev, pending, self.fft_size, self.hop, frame_start, ends)
             front.load_tail(None if state is None else state.tail)
-            if state is None:
-                old = torch.zeros((S, H), dtype=f64, device=dev)
-            else:                                                    # a copy: the caller's state is not modified
-                old = torch.as_tensor(state.old_column).to(device=dev, dtype=f64).reshape(S, H).clone()
+            old = carried(dev, None if state is None else state.old_column, (S, H))
             pixels = torch.empty((S, H, Po), dtype=torch.int32, device=dev)          # uint32 words (torch has no uint32 arithmetic)
             if R:
                 old_next = torch.empty_like(old)
@@ -346,8 +342,8 @@ class SpectrogramBatch:
             new_tail, pending = front.new_tail()
             new_state = SpectrogramState(new_tail, pending, old, table.orig_index, table.resampled_index)
             if is_np:
-                pixels = pixels.cpu().numpy().view(np.uint32)
-                new_state = new_state._replace(tail=new_tail.cpu().numpy(), old_column=old.cpu().numpy())
+                pixels, new_state = to_host((pixels, new_state))
+                pixels = pixels.view(np.uint32)
             else:
                 pixels = pixels.view(torch.uint32) if hasattr(torch, "uint32") else pixels
         if squeeze:

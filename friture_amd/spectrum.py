@@ -17,7 +17,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _lib, tables
-from ._batchio import RecordingFront, check_samples, frame_schedule, null_stream
+from ._batchio import RecordingFront, carried, check_keep, check_samples, frame_schedule, null_stream, to_host
 from .audioproc import audioproc
 from .constants import SAMPLING_RATE
 from .ringbuffer import RingBuffer
@@ -270,8 +270,7 @@ class SpectrumBatch:
         return x, is_np, squeeze, pending
 
     def run(self, x, chunk=512, ends=None, state=None, keep="all", scratch_bytes=1 << 30):
-        if keep not in ("all", "last"):
-            raise ValueError(f"keep={keep!r} ('all' or 'last')")
+        check_keep(keep, "all", "last")
         x, is_np, squeeze, pending = self._check_input(x, state)
         frame_start, refresh_chunk = self.schedule(x.shape[-1], chunk, ends, state)
         import torch
@@ -280,10 +279,7 @@ class SpectrumBatch:
         f64, vp = torch.float64, ctypes.c_void_p
         with null_stream(x, is_np) as dev:
             front = RecordingFront(x, is_np, dev, pending, self.fft_size, self.hop, frame_start, ends)
-            if state is None:
-                sm = torch.zeros((S, rows, B), dtype=f64, device=dev)
-            else:                                                    # a copy: the caller's state is not modified
-                sm = torch.as_tensor(state.smoothed).to(device=dev, dtype=f64).reshape(S, rows, B).clone()
+            sm = carried(dev, None if state is None else state.smoothed, (S, rows, B))
             front.load_tail(None if state is None else state.tail)
             Ro = R if keep == "all" else min(R, 1)
             db = torch.empty((S, Ro, B), dtype=f64, device=dev)
@@ -309,9 +305,8 @@ class SpectrumBatch:
             new_tail, pending = front.new_tail()
             new_state = SpectrumState(sm, new_tail.reshape(S, rows, new_tail.shape[1]), pending)
             if is_np:
-                db, peak, pitch = db.cpu().numpy(), peak.cpu().numpy(), pitch.cpu().numpy()
+                db, peak, pitch, new_state = to_host((db, peak, pitch, new_state))
                 fmax_hz, fpitch_hz = self.freq[peak], np.maximum(self.freq[pitch], 1e-20)
-                new_state = SpectrumState(sm.cpu().numpy(), new_state.tail.cpu().numpy(), pending)
             else:
                 fd = self._table(dev, "freq", self.freq)
                 fmax_hz, fpitch_hz = fd[peak.long()], torch.clamp_min(fd[pitch.long()], 1e-20)

@@ -37,6 +37,8 @@ RECORDERS = {       # module -> the fixtures it records
     "golden_scope": ("scope",),
     "golden_plotcurves": ("plotcurves",),
     "golden_spectrogrambatch": ("spectrogrambatch",),
+    "golden_pitchbatch": ("pitchbatch",),
+    "golden_octavespectrumbatch": ("octavespectrumbatch",),
     "golden_tables": ("filter_tables",),
 }
 

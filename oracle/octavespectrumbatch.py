@@ -1,20 +1,29 @@
-"""What the OctaveSpectrumBatch tests share: a numpy replay of the octave-spectrum widget's chain (oracle.dsp: OlaBank,
-band_smoothing_setup, band_energies, band_db) fed chunk by chunk at given ends with a carried state, the same chain walked in
-256-sample sub-blocks, and seeded inputs."""
+"""What the OctaveSpectrumBatch tests and their recorder (oracle/golden_octavespectrumbatch.py) share: a numpy replay of the
+octave-spectrum widget's chain (oracle.dsp: OlaBank, band_smoothing_setup, band_energies, band_db) fed chunk by chunk at given ends with a carried state, the same chain walked in
+256-sample sub-blocks, and seeded inputs.  tests/golden/octavespectrumbatch.npz pins the replay to the reference widget.  Nothing
+here touches the GPU."""
 import functools
 
 import numpy as np
 
-from conftest import synth
-from oracle import cases, dsp
+from . import dsp
+from .cases import synth
 
 LENGTHS = (256, 512, 768, 1024)
+GOLDEN_CASES = [(bpo, weighting) for bpo in (1, 3) for weighting in (0, 1)]      # on golden_input(), chunks at golden_ends()
 
 
 def sweep(n, seed):
     """Seeded float32 PCM: a 20 Hz - 20 kHz sine sweep plus noise at amplitude 0.25, so that every octave responds."""
-    assert np.array_equal(synth("noise", 64, seed), cases.synth("noise", 64, seed))
     return (0.5 * synth("chirp", n, seed) + synth("noise", n, seed)).astype(np.float32)
+
+
+def golden_input():
+    return sweep(16384, 5).astype(np.float64)
+
+
+def golden_ends():
+    return mixed_ends(16384, 9)
 
 
 def streams(S, n, seed):

@@ -3,7 +3,8 @@
 candidate of oracle.dsp on row 0 of every frame, the level over ALL rows of the frame (:407), oracle.dsp.PitchGate, the
 estimate ring (friture_amd.ringbuffer.RingBuffer, as out_buf) and the OctaveC axis of coordinateTransform.py:73-83 with length 1
 and borders 0.  The frames are cut from the true samples: what the reference's input ring hands out while chunk + fft_size stays
-within its 10000 samples.  Shared by tests/test_pitchbatch_cpu.py and tests/test_pitchbatch_gpu.py.
+within its 10000 samples.  Shared by the PitchBatch tests and their recorder (oracle/golden_pitchbatch.py), which pins this
+replay to the reference's PitchTracker in tests/golden/pitchbatch.npz.  Nothing here touches the GPU.
 """
 import functools
 import math
@@ -11,7 +12,9 @@ import math
 import numpy as np
 
 from friture_amd.ringbuffer import RingBuffer
-from oracle import dsp
+
+from . import dsp
+from .cases import chunk_ends
 
 EPS = np.finfo(np.float64).eps
 
@@ -129,3 +132,19 @@ def ragged(T, seed, largest=3000):
     rng = np.random.default_rng(seed)
     ends = np.unique(np.concatenate([np.cumsum(rng.integers(0, largest, 4 * T // largest + 8)), [T]]))
     return ends[ends <= T]
+
+
+# ---- what tests/golden/pitchbatch.npz records: the reference's PitchTracker behind a reference RingBuffer, chunk by chunk --------
+
+GOLDEN_SETTINGS = dict(fft_size=1024, overlap=0.75, duration=0.1)
+GOLDEN_CHUNKINGS = {"chunk512": lambda T: chunk_ends(T, 512), "ragged": lambda T: ragged(T, 5, largest=2500)}
+GOLDEN_KEYS = {"steady220": "N1024_steady220_x", "jump": "N1024_jump_x", "quiet": "N1024_quiet_x"}      # inputs that lie in pitch.npz
+
+
+def golden_inputs(pitch_npz):
+    """{case: x [rows, n] float64}: the three one-row cases are arrays of pitch.npz (GOLDEN_KEYS), the three two-row cases stand
+    `jump` beside a seeded tone and take the two dual_inputs."""
+    one = {name: pitch_npz[key].astype(np.float64)[None] for name, key in GOLDEN_KEYS.items()}
+    n = one["jump"].shape[1]
+    return {**one, "jump_tone": np.stack([one["jump"][0], tone(n, 330.0, -30.0, 21)]), "dual_one": dual_inputs(n)[0],
+            "dual_two": dual_inputs(n)[1]}

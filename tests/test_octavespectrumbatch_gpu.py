@@ -1,12 +1,12 @@
 """OctaveSpectrumBatch on the GPU (octspecbatch.hip over the FFT overlap-add bank) against the numpy replay of the widget's chain
-(octavespectrumbatch_helpers, pinned to the reference in test_octavespectrumbatch_cpu.py) and against itself.
+(oracle/octavespectrumbatch.py, pinned to the reference by tests/golden/octavespectrumbatch.npz) and against itself.
 
 Bars, the project's own for this bank (tests/test_ola_gpu.py): energies |got - want| <= 1e-10 want + 1e-20 max(want); dB against
 10 log10(energy_got + 1e-30) + w formed in numpy from the returned energies: 1e-12 absolute (a few ulp at magnitudes up to 300)."""
 import numpy as np
 import pytest
 
-import octavespectrumbatch_helpers as H
+from oracle import octavespectrumbatch as H
 
 pytestmark = pytest.mark.gpu
 T0 = 8192 + 768         # crosses the bank's 3072-output set at stages 0 and 1 and leaves a pending remainder

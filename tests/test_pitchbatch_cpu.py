@@ -1,13 +1,12 @@
 """PitchBatch without a GPU: the refresh schedule against a literal chunk loop of new_frames(), the history length, the
-properties of the numpy replay (tests/pitchbatch_helpers.py) that the GPU tests lean on, and — where the reference checkout is
-present — that replay against the reference's own PitchTracker fed chunk by chunk, with one row and with two."""
+properties of the numpy replay (oracle/pitchbatch.py) that the GPU tests lean on, and that replay against the recording of the
+reference's own PitchTracker fed chunk by chunk, with one row and with two (tests/golden/pitchbatch.npz)."""
 import numpy as np
 import pytest
 
-import pitchbatch_helpers as H
 from friture_amd._batchio import chunk_ends
 from friture_amd.pitch_tracker import PitchBatch, PitchState, pitch_schedule
-from oracle import refshim
+from oracle import pitchbatch as H
 
 TOL_F0 = 1e-9                                        # tests/test_pitch_gpu.py
 
@@ -110,35 +109,32 @@ def test_dual_inputs_sit_a_decibel_away_from_the_threshold_on_opposite_sides(fft
     assert np.all(np.isnan(two["estimates"])) and np.all(two["raw"][1] >= 0.5)       # unvoiced by the level alone
 
 
-@pytest.mark.skipif(not refshim.available(), reason="needs the reference checkout")
 @pytest.mark.parametrize("rows", [1, 2])
 def test_replay_equals_the_reference_tracker_fed_chunk_by_chunk(golden, rows):
-    from oracle.golden_pitch import import_reference_pitch_tracker
-    pt = import_reference_pitch_tracker()
-    from friture.ringbuffer import RingBuffer
-    g = golden("pitch")
-    fft_size, overlap, duration = 1024, 0.75, 0.1
-    cases = {name: g[f"N1024_{name}_x"].astype(np.float64) for name in ("steady220", "jump", "quiet")}
-    if rows == 2:
-        n = len(cases["jump"])
-        cases = {"jump": np.stack([cases["jump"], H.tone(n, 330.0, -30.0, 21)]), "one": H.dual_inputs(n)[0], "two": H.dual_inputs(n)[1]}
+    """The replay against what the reference's PitchTracker behind a reference RingBuffer returned chunk by chunk
+    (oracle/golden_pitchbatch.py): update()'s flag and the get_estimates window per chunk, the latest estimate per refresh, the
+    joined estimates and the frame count."""
+    g = golden("pitchbatch")
+    assert H.GOLDEN_SETTINGS == dict(fft_size=1024, overlap=0.75, duration=0.1)
+    cases = {name: x for name, x in H.golden_inputs(golden("pitch")).items() if x.shape[0] == rows}
+    assert list(cases) == (["steady220", "jump", "quiet"] if rows == 1 else ["jump_tone", "dual_one", "dual_two"])
     for name, x in cases.items():
-        x = np.atleast_2d(x)
-        for ends in (chunk_ends(x.shape[1], 512), H.ragged(x.shape[1], 5, largest=2500)):
-            ring = RingBuffer()
-            tracker = pt.PitchTracker(ring, fft_size=fft_size, overlap=overlap)
-            mine = H.WidgetReplay(fft_size=fft_size, overlap=overlap, duration=duration)
+        assert rows == 2 or str(g[f"{name}_x_key"]) == f"N1024_{name}_x"
+        for chunking, ends in (("chunk512", chunk_ends(x.shape[1], 512)), ("ragged", H.ragged(x.shape[1], 5, largest=2500))):
+            want = {k: g[f"{name}_{chunking}_{k}"] for k in ("ends", "fresh", "windows", "latest", "estimates")}
+            assert np.array_equal(ends, want["ends"]) and np.array_equal(ends, H.GOLDEN_CHUNKINGS[chunking](x.shape[1]))
+            mine = H.WidgetReplay(**H.GOLDEN_SETTINGS)
             start, estimates = 0, []
-            for e in ends.tolist():
-                ring.push(x[:, start:e], 0.)
-                fresh = tracker.update()
+            for c, e in enumerate(ends.tolist()):
+                fresh = bool(want["fresh"][c])
                 assert mine.push(x[:, start:e]) == fresh, (name, e)
-                window = tracker.get_estimates(duration)
+                window = want["windows"][c]
                 assert H.close(mine.get_estimates(), window, TOL_F0), (name, e)
                 if fresh:
-                    latest = tracker.get_latest_estimate()
-                    assert H.close(mine.pitch[-1], latest, TOL_F0)
+                    assert H.close(mine.pitch[-1], want["latest"][len(estimates)], TOL_F0)
                     estimates.append(window[len(window) - (mine.frame_start[-1] - mine.frame_start[-2]):])
                 start = e
+            assert len(estimates) == len(want["latest"]) == int(want["fresh"].sum())
             assert H.close(np.array(mine.estimates), np.concatenate(estimates), TOL_F0), name
-            assert len(mine.estimates) == (x.shape[1] - fft_size) // mine.step + 1
+            assert H.close(np.array(mine.estimates), want["estimates"], TOL_F0), name
+            assert len(mine.estimates) == (x.shape[1] - 1024) // mine.step + 1

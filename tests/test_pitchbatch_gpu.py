@@ -1,5 +1,5 @@
-"""PitchBatch on the GPU against the numpy replay of the widget chain (tests/pitchbatch_helpers.py, pinned to the reference's own
-PitchTracker by tests/test_pitchbatch_cpu.py) and against PitchEngine.track.
+"""PitchBatch on the GPU against the numpy replay of the widget chain (oracle/pitchbatch.py, pinned to the reference's own
+PitchTracker by tests/golden/pitchbatch.npz, which oracle/golden_pitchbatch.py records) and against PitchEngine.track.
 
 Tolerances are those of tests/test_pitch_gpu.py: estimates and `pitch` 1e-9 relative, confidence 1e-11, level 1e-10 dB, the
 voiced pattern identical; the raw estimate is not compared on `noise` (its arg-max sits among near-ties).  The curve is held to
@@ -11,7 +11,7 @@ import functools
 import numpy as np
 import pytest
 
-import pitchbatch_helpers as H
+from oracle import pitchbatch as H
 from friture_amd._batchio import chunk_ends
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +32,7 @@ def pt(hip):
 
 @functools.lru_cache(maxsize=None)
 def _golden():
-    with np.load(H.__file__.rsplit("/", 1)[0] + "/golden/pitch.npz", allow_pickle=False) as z:
+    with np.load(__file__.rsplit("/", 1)[0] + "/golden/pitch.npz", allow_pickle=False) as z:
         return {k: z[k] for k in z.files if k.endswith("_x")}
 
 
