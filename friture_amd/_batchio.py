@@ -1,8 +1,9 @@
-"""What the batch classes (LevelsBatch, ScopeBatch, CurveBatch, SpectrumBatch, SpectrogramBatch, PitchBatch, OctaveSpectrumBatch)
-share: their input is a float32/float64 numpy array or CUDA tensor, their results are of the same kind, and a recording is seen
-in chunks (chunk_ends, checked_ends, frame_schedule); for the four chains over recordings, the host side of run(): the input
-checks (check_keep, check_samples), the hand-over to the null stream, the device copy of a carried state (carried) and the way
-back to numpy (to_host); for the two STFT chains, the sample front (RecordingFront)."""
+"""What the batch classes (LevelsBatch, ScopeBatch, CurveBatch, SpectrumBatch, SpectrogramBatch, PitchBatch, OctaveSpectrumBatch,
+DelayEstimatorBatch) share: their input is a float32/float64 numpy array or CUDA tensor, their results are of the same kind, and a
+recording is seen in chunks (chunk_ends, checked_ends, frame_schedule); for the five chains over recordings, the host side of
+run(): the input checks (check_keep, check_samples; `dual` for the delay estimator's two rows per stream), the hand-over to the
+null stream, the device copy of a carried state (carried) and the way back to numpy (to_host); for the two STFT chains, the sample
+front (RecordingFront)."""
 from __future__ import annotations
 
 import ctypes

@@ -140,6 +140,12 @@ SIGNATURES = {
                                    c_void_p, c_int, c_double, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "frt_specgram_batch": (c_int, [c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                    c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64]),
+    "frt_delaybatch_decimate": (c_int, [POINTER(c_double), POINTER(c_double), c_int, c_int, c_void_p, c_int, c_int, c_int64, c_int64,
+                                        c_int64, c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
+    "frt_delaybatch_windows": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int64, POINTER(c_int64), c_void_p, c_void_p, c_int64,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
+    "frt_delaybatch_readout": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_double, c_double, c_double,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

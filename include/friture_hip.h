@@ -302,6 +302,41 @@ typedef struct frt_delay_readout {
 int frt_gcc_readout(frt_gcc* h, const double* xcorr, const double* old_smoothed, double alpha, double sample_rate,
                     double delayrange_s, double* smoothed_out, frt_delay_readout* readout);
 
+/* ---- the delay estimator's chain over whole recordings (delaybatch.hip) -----------------------------------------------
+ * Three steps of DelayEstimatorBatch (friture_amd/delay_estimator.py); everything is enqueued on the null stream, every
+ * array is DEVICE memory unless said otherwise, float64 unless said otherwise.
+ *
+ * frt_delaybatch_decimate: decimate_multiple (friture/signal/decimate.py:45-71) of x [n_channels][n] (rows x_stride elements
+ * apart; dtype 0 float32, widened exactly, 1 float64), time-parallel: every stage cuts its input into cells of 1024 samples
+ * on a grid anchored at sample `origin` >> stage of the recording (origin: the absolute index of x's first sample), runs the
+ * cells from the zero state, chains their end states with the exact transition A^1024 and runs them again from their true
+ * start states.  b, a: the decimator's 13 + 13 coefficients (HOST, a[0] = 1).  zi / zf: [n_channels][n_stages][12] DF2T
+ * states in decimate_multiple's order, NULL = zero state / not wanted.  out: [n_channels][*n_out], rows out_stride apart,
+ * *n_out = n halved n_stages times, rounding up. */
+int frt_delaybatch_decimate(const double* b, const double* a, int n_coef, int n_stages, const void* x, int dtype, int n_channels,
+                            int64_t n, int64_t x_stride, int64_t origin, const double* zi, double* out, int64_t out_stride,
+                            double* zf, int64_t* n_out);
+/* The windows of n_streams delay estimators and their GCC-PHAT.  dec: [n_streams][2][n_dec] decimated signals behind the
+ * carried tail, rows dec_stride apart.  runs: HOST [n_windows][8][4] int64 (delay_schedule): per window up to eight runs of
+ * (first source index in a row of dec, length, 1 = zeros instead, earlier window whose mean the ring view had subtracted: its
+ * index in this call, -1 none, -2 the window before this call's first: means_in [n_streams][2], NULL = zeros); the lengths of
+ * a window add up to `length`.  means_out: [n_streams][n_windows][2] the effective windows' means (0 where gated); gated_out:
+ * [n_streams][n_windows] 1 where every effective sample of a channel is equal.  xcorr: [n_streams][n_windows][length], pair
+ * q = stream * n_windows + window.  The pairs go to frt_gcc_phat in slabs of pairs_full (<= 65535) on gcc_full, a handle of
+ * that many pairs, and a shorter last slab on gcc_last, a handle of its size (both on the null stream). */
+int frt_delaybatch_windows(const double* dec, int64_t dec_stride, int64_t n_dec, int n_streams, int length, int64_t n_windows,
+                           const int64_t* runs, const double* means_in, frt_gcc* gcc_full, int64_t pairs_full, frt_gcc* gcc_last,
+                           double* xcorr, double* means_out, int* gated_out, int* n_slabs_out);
+/* Smoothing and read-out of every window in order (friture/delay_estimator.py:134-182): smoothed = alpha xcorr + (1 - alpha)
+ * smoothed from the first ungated window on (itself where no correlation is carried: smoothed_in [n_streams][length] with
+ * present_in [n_streams] != 0, either may be NULL); gated windows keep it and read 0.  Per window [n_streams][n_windows]:
+ * argmax of |smoothed| (the first on ties), delay_ms, distance_m, extremum, correlation as frt_delay_readout has them.
+ * smoothed_out / present_out: the correlation carried out.  Partial sums are combined in lag order. */
+int frt_delaybatch_readout(const double* xcorr, const int* gated, int n_streams, int64_t n_windows, int length,
+                           const double* smoothed_in, const int* present_in, double alpha, double sample_rate, double delayrange_s,
+                           double* smoothed_out, int* present_out, int* argmax_out, double* delay_ms_out, double* distance_m_out,
+                           double* extremum_out, int* correlation_out);
+
 /* ---- K6: screen-space stages of the spectrogram, and block-wise exponential smoothing -------------
  * Stateless float64 kernels, one per block of the reference's Transform_Pipeline
  * (friture/signal/transform_pipeline.py:23-34); the stateful bookkeeping of the online resampler
