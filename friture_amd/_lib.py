@@ -106,6 +106,15 @@ SIGNATURES = {
                                      c_void_p, c_void_p, POINTER(c_int64)]),
     "frt_pitch_refresh": (c_int, [c_void_p, c_int, c_int64, POINTER(c_int64), c_int64, c_void_p, c_int64, c_double, c_double, c_int,
                                   c_void_p, c_void_p, c_void_p]),
+    "frt_pitch_live_create": (c_int, [POINTER(c_void_p), c_void_p, c_int64, c_double, c_double]),
+    "frt_pitch_live_destroy": (None, [c_void_p]),
+    "frt_pitch_live_reset": (c_int, [c_void_p]),
+    "frt_pitch_live_push": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_double, c_double, c_double, c_void_p,
+                                    POINTER(c_double), c_void_p, POINTER(c_int64)]),
+    "frt_pitch_live_get_state": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "frt_pitch_live_set_state": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "frt_pitch_live_set_crossover": (c_int, [c_void_p, c_int]),
+    "frt_pitch_live_crossover": (c_int, [c_void_p]),
     "frt_delay_create": (c_int, [POINTER(c_void_p), POINTER(c_double), POINTER(c_double), c_int, c_int]),
     "frt_delay_destroy": (None, [c_void_p]),
     "frt_delay_stream": (c_void_p, [c_void_p]),

@@ -36,7 +36,7 @@ CXXFLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-W
 EXTRA_FLAGS = {"iir.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form"], "pipeline.hip": ["-ffp-contract=off"], "pitch.hip": ["-ffp-contract=off"],
                "specgram.hip": ["-ffp-contract=off"], "levels.hip": ["-ffp-contract=off"], "scope.hip": ["-ffp-contract=off"],
                "curves.hip": ["-ffp-contract=off"], "spectrumbatch.hip": ["-ffp-contract=off"], "specgrambatch.hip": ["-ffp-contract=off"],
-               "pitchbatch.hip": ["-ffp-contract=off"], "octspecbatch.hip": ["-ffp-contract=off"], "delaybatch.hip": ["-ffp-contract=off"],
+               "pitchbatch.hip": ["-ffp-contract=off"], "pitchstream.hip": ["-ffp-contract=off"], "octspecbatch.hip": ["-ffp-contract=off"], "delaybatch.hip": ["-ffp-contract=off"],
                "stft.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"]}
 
 

@@ -21,6 +21,7 @@
 #include <limits>
 
 #include "common.h"
+#include "pitch_device.h"
 #include "pitch_plan.h"
 
 namespace frt {
@@ -45,12 +46,6 @@ struct PitchArgs {
     long long F, f_start, Fc;  // frames per channel in total / first frame of this chunk / frames in this chunk
     double binw;              // sample_rate / N
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-    // fixed-order butterfly: every lane ends with the same, scheduling-independent sum
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // |rfft| on the log grid: np.interp(freqs, k * binw, |X|)  (pitch_tracker.py:370-378)
 __device__ __forceinline__ double grid_value(const PitchArgs& a, const double* P, int l) {
@@ -289,61 +284,21 @@ __global__ void __launch_bounds__(256) pitch_strength_kernel(const double* __res
     }
 }
 
-// np.argmax ordering: the first NaN wins, otherwise the first maximum
-__device__ __forceinline__ bool argmax_before(double va, int ia, double vb, int ib) {
-    const bool na = va != va, nb = vb != vb;
-    if (na || nb) return na && (!nb || ia < ib);
-    return va > vb || (va == vb && ia < ib);
-}
-
 // One wavefront per frame.
 __global__ void __launch_bounds__(256) pitch_pick_kernel(const PitchArgs a) {
     const long long gf = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gf >= (long long)a.C * a.Fc) return;
     const int lane = threadIdx.x & 63;
     const double* st = a.strength + gf * a.Kp;
-    double best = st[lane < a.K ? lane : 0];
-    int bi = lane < a.K ? lane : 0;
-    for (int c = lane + 64; c < a.K; c += 64) {
-        const double v = st[c];
-        if (argmax_before(v, c, best, bi)) { best = v; bi = c; }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (argmax_before(ov, oi, best, bi)) { best = ov; bi = oi; }
-    }
+    double best;
+    int bi;
+    pick_argmax(st, a.K, lane, best, bi);
     if (lane != 0) return;
-    double shift = 0.0;
-    if (bi > 0 && bi < a.K - 1) {                               // :392-398, fastParabolicInterp :187-191
-        const double y1 = st[bi - 1], y2 = st[bi], y3 = st[bi + 1];
-        const double pa = (y1 - 2 * y2 + y3) / 2;
-        const double pb = (y3 - y1) / 2;
-        shift = -pb / (2 * pa + std::numeric_limits<double>::epsilon());
-    }
-    // np.interp(idx + shift, arange(L), freqs)   (:402)
-    const double xq = (double)bi + shift;
-    double f0;
-    if (xq != xq) {
-        f0 = xq;
-    } else if (xq < 0.0) {
-        f0 = a.freqs[0];
-    } else if (xq >= (double)(a.L - 1)) {
-        f0 = a.freqs[a.L - 1];
-    } else {
-        const int j = (int)floor(xq);
-        const double fj = a.freqs[j];
-        if ((double)j == xq) {
-            f0 = fj;
-        } else {
-            const double slope = (a.freqs[j + 1] - fj) / ((double)(j + 1) - (double)j);
-            f0 = slope * (xq - (double)j) + fj;
-        }
-    }
+    const double f0 = pick_frequency(st, bi, a.K, a.L, a.freqs);
     const int chan = (int)(gf / a.Fc);
     const long long f = a.f_start + (gf - (long long)chan * a.Fc);
     a.raw[(0ll * a.C + chan) * a.F + f] = f0;
-    a.raw[(1ll * a.C + chan) * a.F + f] = best / 2.56;          // :412
+    a.raw[(1ll * a.C + chan) * a.F + f] = pick_confidence(best);
 }
 
 // The voiced / unvoiced gate and its carried state (:405-428).  prev = NaN encodes "no previous estimate".
@@ -353,22 +308,6 @@ __global__ void __launch_bounds__(256) pitch_pick_kernel(const PitchArgs a) {
 // segment of frames into a map {unvoiced, voiced} -> {unvoiced, voiced}, the maps are chained, and the
 // segment is replayed with its true incoming state.
 constexpr int kGateThreads = 256;
-
-struct GateFrame {
-    bool ok, jump_ok;
-    double f0;
-};
-
-__device__ __forceinline__ GateFrame gate_frame(const double* raw, int C, long long F, int chan, long long f, double before,
-                                                double min_db, double conf, double p_delta) {
-    GateFrame g;
-    g.f0 = raw[(0ll * C + chan) * F + f];
-    const double cf = raw[(1ll * C + chan) * F + f];
-    const double db = raw[(2ll * C + chan) * F + f];
-    g.ok = !((db < min_db) || (cf < conf));
-    g.jump_ok = !(12.0 * fabs(log2(g.f0 / before)) > p_delta);
-    return g;
-}
 
 __global__ void __launch_bounds__(kGateThreads) pitch_gate_kernel(const double* raw, int C, long long F, double min_db,
                                                                   double conf, double p_delta, double* prev, double* f0_out) {
@@ -541,6 +480,19 @@ extern "C" int frt_pitch_track(frt_pitch* h, const double* x, int64_t T, int64_t
     return pitch_track_with_level(h, x, T, x_stride, f0_out, raw_out, n_frames_out, nullptr);
 }
 
+// the log-grid kernel over every 8-frame group that `blocks` strength blocks touch, and the tiled strength kernel over them
+static void launch_loggrid(const frt_pitch* h, const PitchArgs& a, unsigned blocks) {
+    if (h->Lp == 1024 && option(kOptPitchGridTwoPass) <= 0)
+        hipLaunchKernelGGL(pitch_loggrid_reg_kernel<32>, dim3(blocks * (kFramesPerBlock / kFramesPerGroup)), dim3(256), 0, h->stream, a);
+    else
+        hipLaunchKernelGGL(pitch_loggrid_kernel, dim3(blocks * (kFramesPerBlock / kFramesPerGroup)), dim3(256), 0, h->stream, a);
+}
+
+static void launch_strength(const frt_pitch* h, const PitchArgs& a, unsigned blocks, long long total) {
+    hipLaunchKernelGGL(pitch_strength_kernel, dim3(blocks, h->Kp / kCandPerWave), dim3(256), 0, h->stream, a.kt, a.s, a.strength, h->lrange.as<int>(),
+                       h->L, h->Lp, h->Kp, total);
+}
+
 void frt::pitch_plan_shape(const frt_pitch* h, int* fft_size, int* hop, int* n_channels) {
     *fft_size = h->N;
     *hop = h->hop;
@@ -602,10 +554,7 @@ int frt::pitch_track_with_level(frt_pitch* h, const double* x, int64_t T, int64_
         const unsigned groups = (unsigned)((total + kFramesPerGroup - 1) / kFramesPerGroup);
         const unsigned blocks = (unsigned)((total + kFramesPerBlock - 1) / kFramesPerBlock);
         // the strength kernel reads whole 8-frame groups: have the grid kernel fill every group a block touches
-        if (h->Lp == 1024 && option(kOptPitchGridTwoPass) <= 0)
-            hipLaunchKernelGGL(pitch_loggrid_reg_kernel<32>, dim3(blocks * (kFramesPerBlock / kFramesPerGroup)), dim3(256), 0, h->stream, a);
-        else
-            hipLaunchKernelGGL(pitch_loggrid_kernel, dim3(blocks * (kFramesPerBlock / kFramesPerGroup)), dim3(256), 0, h->stream, a);
+        launch_loggrid(h, a, blocks);
         if (level) {
             // filled once for all frames, below
         } else if (h->N % h->hop == 0 && h->N / h->hop >= 2) {
@@ -619,8 +568,7 @@ int frt::pitch_track_with_level(frt_pitch* h, const double* x, int64_t T, int64_
         } else {
             hipLaunchKernelGGL(pitch_level_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, h->stream, a);
         }
-        hipLaunchKernelGGL(pitch_strength_kernel, dim3(blocks, h->Kp / kCandPerWave), dim3(256), 0, h->stream, a.kt, a.s, a.strength, h->lrange.as<int>(),
-                           h->L, h->Lp, h->Kp, total);
+        launch_strength(h, a, blocks, total);
         hipLaunchKernelGGL(pitch_pick_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, h->stream, a);
         FRT_HIP_CHECK(hipGetLastError());
         (void)groups;
@@ -637,5 +585,54 @@ int frt::pitch_track_with_level(frt_pitch* h, const double* x, int64_t T, int64_
         FRT_HIP_CHECK(hipMemcpyAsync(f0_out, df0, out_n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
     }
+    return FRT_OK;
+}
+
+// ---- what the live chain (pitchstream.hip) uses: pitch_plan.h ---------------------------------------------------------------------
+
+static PitchArgs live_args(const frt_pitch* h, const double* x, int64_t x_stride, long long F) {
+    PitchArgs a{};
+    a.x = x; a.x_stride = x_stride; a.psd = h->psd.as<double>(); a.s = h->s.as<double>();
+    a.strength = h->strength.as<double>(); a.raw = nullptr; a.freqs = h->freqs.as<double>();
+    a.jidx = h->jidx.as<int>(); a.kt = h->kt.as<double>();
+    a.N = h->N; a.nb = h->N / 2 + 1; a.hop = h->hop; a.L = h->L; a.Lp = h->Lp; a.K = h->K; a.Kp = h->Kp; a.C = 1;
+    a.F = F; a.f_start = 0; a.Fc = F; a.binw = h->fs / (double)h->N;
+    return a;
+}
+
+int frt::pitch_live_front(frt_pitch* h, const double* x, int64_t span, int64_t x_stride, int64_t n_frames, hipStream_t stream,
+                          PitchLiveView* view) {
+    FRT_REQUIRE(h && x && view, "pitch_live_front: null argument");
+    FRT_REQUIRE(h->C == 1, "pitch_live_front: a plan of %d channels (one wanted)", h->C);
+    FRT_REQUIRE(n_frames >= 1 && span == h->N + (n_frames - 1) * (int64_t)h->hop,
+                "pitch_live_front: %lld samples for %lld frames of %d every %d", (long long)span, (long long)n_frames, h->N, h->hop);
+    int rc;
+    if ((rc = frt_pitch_set_stream(h, stream))) return rc;
+    const int nb = h->N / 2 + 1;
+    const long long padded = (n_frames + kFramesPerBlock - 1) / kFramesPerBlock * kFramesPerBlock;
+    if ((rc = h->psd.reserve((size_t)n_frames * nb * sizeof(double))) ||
+        (rc = h->s.reserve(((size_t)padded * h->Lp + 4 * kFramesPerGroup) * sizeof(double))) ||
+        (rc = h->strength.reserve((size_t)padded * h->Kp * sizeof(double))))
+        return rc;
+    int64_t got = 0;
+    if ((rc = frt_stft_run(h->stft, FRT_STFT_PSD, x, span, x_stride, h->psd.ptr, &got))) return rc;
+    FRT_REQUIRE(got == n_frames, "pitch_live_front: internal frame count mismatch");
+    launch_loggrid(h, live_args(h, x, x_stride, n_frames), (unsigned)(padded / kFramesPerBlock));
+    FRT_HIP_CHECK(hipGetLastError());
+    view->s = h->s.as<double>();
+    view->strength = h->strength.as<double>();
+    view->kt = h->kt.as<double>();
+    view->freqs = h->freqs.as<double>();
+    view->lrange = h->lrange.as<int>();
+    view->N = h->N; view->hop = h->hop; view->L = h->L; view->Lp = h->Lp; view->K = h->K; view->Kp = h->Kp;
+    view->cand_per_range = kCandPerWave;
+    return FRT_OK;
+}
+
+int frt::pitch_live_strength_tiled(frt_pitch* h, int64_t n_frames) {
+    FRT_REQUIRE(h && h->C == 1 && n_frames >= 1 && h->strength.ptr, "pitch_live_strength_tiled: no front before it");
+    const long long padded = (n_frames + kFramesPerBlock - 1) / kFramesPerBlock * kFramesPerBlock;
+    launch_strength(h, live_args(h, nullptr, 0, n_frames), (unsigned)(padded / kFramesPerBlock), n_frames);
+    FRT_HIP_CHECK(hipGetLastError());
     return FRT_OK;
 }

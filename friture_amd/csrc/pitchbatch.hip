@@ -17,6 +17,7 @@
 #include <limits>
 
 #include "common.h"
+#include "pitch_device.h"
 #include "pitch_plan.h"
 #include "widget_device.h"
 
@@ -37,16 +38,6 @@ template <bool kF64>
 __device__ __forceinline__ double row_sample(const RowsSource& p, int s, int row, long long i) {
     if (i < p.pending) return p.tail[((long long)s * p.rows + row) * p.pending + i];
     return load_real<kF64>(p.x, (long long)s * p.ld_stream + (long long)row * p.ld_row + (i - p.pending));
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    // fixed-order butterfly: every lane ends with the same, scheduling-independent sum
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double level_db(double energy, double count) {
-    return 20.0 * log10(sqrt(energy / count) + std::numeric_limits<double>::epsilon());
 }
 
 // eb[(s * rows + row) * n_blocks + b] = sum of squares of samples [b * hop, (b + 1) * hop).  One wavefront per block.
@@ -149,8 +140,7 @@ __global__ void __launch_bounds__(kThreads) pitch_axis_kernel(const double* __re
     const long long n = p.M + p.F;
     if (i < n) {
         const double v = i < p.M ? history_in[s * p.M + i] : est[s * p.F + (i - p.M)];
-        const double t = (log2(fmax(v, 1e-20)) - p.trans_min) / p.trans_span;
-        y[s * n + i] = fmin(fmax(1.0 - t, 0.0), 1.0);
+        y[s * n + i] = axis_value(v, p.trans_min, p.trans_span);
         if (i >= p.F) history_out[s * p.M + (i - p.F)] = v;
     } else if (i < n + p.R) {
         const long long r = i - n;

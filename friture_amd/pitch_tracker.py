@@ -459,3 +459,226 @@ class PitchBatch:
             est, pitch, curve = est[0], pitch[0], curve[0]
             raw = raw[:, 0] if with_raw else None
         return PitchResult(est, raw, frame_start, refresh_chunk, pitch, curve, self.times, new_state)
+
+
+# ---- the live chain on the device -----------------------------------------------------------------------------------------
+
+class PitchTrackerStream(PitchTracker):
+    """PitchTracker with its chain resident on the device (csrc/pitchstream.hip, frt_pitch_live_*): the reference's interface —
+    the shared host RingBuffer, set_input_buffer, update, get_estimates, get_latest_estimate, estimate_pitch, and min_db / conf /
+    p_delta as plain attributes read at every update — with the gate's previous estimate, the estimate history and the curve
+    kept in HBM.  An update() that completes frames is ONE device call: the span of the ring that completes them goes up (one
+    row, or two when the ring is in dual-channel mode: the gate's level is the RMS over both), the new estimates, the latest
+    estimate and the curve of update_curve come back, behind one synchronisation; an update() that completes none makes no
+    device call.  The estimates still go into out_buf; `pitch`, `curve` and `times` are what handle_new_data / update_curve
+    (:109-119) leave in the view model, as of the last refresh.  duration, min_freq and max_freq are fixed at construction, as
+    in PitchBatch.  The device objects are created at the first completed frame: construction and updates before it need no GPU.
+
+    Estimates, `pitch` and `curve` equal PitchBatch.run on the same samples and chunk ends bit for bit, and get_state() /
+    set_state() exchange a PitchState of one stream with it: a recording can be started in PitchBatch and continued live, or
+    the other way round."""
+
+    def __init__(self, input_buf: RingBuffer, fft_size: int = DEFAULT_FFT_SIZE, overlap: float = 0.75,
+                 sample_rate: int = SAMPLING_RATE, min_freq: float = DEFAULT_MIN_FREQ, max_freq: float = DEFAULT_MAX_FREQ,
+                 min_db: float = DEFAULT_MIN_DB, cres: int = DEFAULT_C_RES, conf: float = DEFAULT_P_CONF,
+                 p_delta: int = DEFAULT_P_DELTA, duration: float = DEFAULT_DURATION):
+        # PitchTracker.__init__ without its audioproc, which is a device object: nothing here touches the GPU
+        self.fft_size = int(fft_size)
+        self.overlap = overlap
+        self.sample_rate = sample_rate
+        self.min_freq, self.max_freq = min_freq, max_freq
+        self.min_db, self.cres, self.conf, self.p_delta = min_db, cres, conf, p_delta
+        self.duration = duration
+        self.step = self._step()
+        if self.step < 1:
+            raise ValueError(f"fft_size {fft_size} with overlap {overlap}: no frame advance")
+        if not 0 < min_freq < max_freq:
+            raise ValueError(f"axis range [{min_freq}, {max_freq}]")
+        self.n_history = math.floor(duration / (self.step / sample_rate)) + 1          # get_estimates, :325-327
+        if self.n_history < 1:
+            raise ValueError(f"duration {duration}")
+        self.times = np.linspace(0, 1.0, self.n_history)
+        self.curve = np.ones(self.n_history)                 # the ring's zeros on the axis
+        self.pitch = math.nan                                # no refresh yet
+
+        self.input_buf = input_buf
+        self.input_buf.grow_if_needed(self.fft_size)
+        self.next_in_offset = self.input_buf.offset
+        self.out_buf = RingBuffer()
+        self.out_offset = self.out_buf.offset
+
+        self._engine, self._live = None, None
+        self._carry = None                                   # [rows, n] float64 handed over by set_state, ahead of the ring's samples
+        self._previous = np.full(1, np.nan)                  # the state while there is no device object
+        self._history = np.zeros(self.n_history)
+        self._init_swipe()
+
+    # ---- host only ------------------------------------------------------------------------------------------------------------
+    def set_input_buffer(self, new_buf: RingBuffer) -> None:
+        super().set_input_buffer(new_buf)
+        self._carry = None
+
+    def _init_swipe(self):
+        if getattr(self, "_live", None) is not None:         # new tables: the plan is rebuilt, the state stays
+            self._previous, self._history = self._device_state()
+        self.close()
+        super()._init_swipe()
+
+    def pending(self) -> int:
+        """Samples received that no frame has consumed."""
+        carried_over = 0 if self._carry is None else self._carry.shape[1]
+        return carried_over + self.input_buf.offset - self.next_in_offset
+
+    def plan_update(self):
+        """(frames, span) of the next update(): the frames the pending samples complete and the samples that hold them."""
+        avail = self.pending()
+        count = 0 if avail < self.fft_size else (avail - self.fft_size) // self.step + 1
+        return count, self.fft_size + (count - 1) * self.step if count else 0
+
+    def _take(self, count, span):
+        """The span that completes `count` frames, [rows, span]; the stream advances by count steps."""
+        used = count * self.step
+        if self._carry is None:
+            run = self.input_buf.data_indexed(self.next_in_offset + span, span)
+            self.next_in_offset += used
+            return run
+        carried_over = self._carry.shape[1]
+        rest = self.input_buf.data_indexed(self.next_in_offset + span - carried_over, span - carried_over)
+        if rest.shape[0] != self._carry.shape[0]:
+            raise ValueError(f"a state of {self._carry.shape[0]} rows ahead of a ring of {rest.shape[0]}")
+        run = np.concatenate([self._carry, rest], axis=1)
+        if used >= carried_over:
+            self.next_in_offset += used - carried_over
+            self._carry = None
+        else:
+            self._carry = self._carry[:, used:]
+        return run
+
+    def update(self) -> bool:
+        assert self.input_buf.offset >= self.next_in_offset
+        count, span = self.plan_update()
+        new = []
+        if count:
+            new = list(self._push(self._take(count, span)))
+        self.out_buf.push(np.array([new]), 0)
+        self.out_offset = self.out_buf.offset
+        return len(new) != 0
+
+    # ---- device ---------------------------------------------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_live", None) is not None:
+            _lib.load().frt_pitch_live_destroy(self._live)
+        self._live = None
+        if getattr(self, "_engine", None) is not None:
+            self._engine.close()
+        self._engine = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _device(self):
+        if self._live is None:
+            lib = _lib.init()
+            self._engine = PitchEngine(self.fft_size, self.step, 1, self.sample_rate, self.logSpacedFreqs, self.kernels,
+                                       self.min_db, self.conf, self.p_delta)
+            live = ctypes.c_void_p()
+            _lib.check(lib.frt_pitch_live_create(ctypes.byref(live), self._engine._h, self.n_history, float(self.min_freq),
+                                                 float(self.max_freq)))
+            self._live = live
+            _lib.check(lib.frt_pitch_live_set_state(live, self._previous.ctypes.data, self._history.ctypes.data))
+        return self._live
+
+    @property
+    def crossover(self) -> int:
+        """Frames per update up to which the few-frames product kernel runs; above it the tiled kernel of PitchEngine."""
+        return int(_lib.load().frt_pitch_live_crossover(self._live))
+
+    @crossover.setter
+    def crossover(self, frames):
+        _lib.check(_lib.load().frt_pitch_live_set_crossover(self._device(), int(frames)))
+
+    def _push(self, samples):
+        """[rows, fft_size + (F - 1) * step] host samples -> the F gated estimates; leaves pitch and curve."""
+        x = np.asarray(samples)
+        if x.ndim == 1:
+            x = x[None, :]
+        if x.dtype not in (np.float32, np.float64):
+            x = x.astype(np.float64)
+        if x.ndim != 2 or x.shape[0] not in (1, 2):
+            raise ValueError(f"samples of shape {x.shape}: one stream is [rows, n] with one row, or two for dual channels")
+        if x.strides[1] != x.itemsize or x.strides[0] % x.itemsize or (x.shape[0] == 2 and x.strides[0] < x.shape[1] * x.itemsize):
+            x = np.ascontiguousarray(x)
+        span = x.shape[1]
+        if span < self.fft_size or (span - self.fft_size) % self.step:
+            raise ValueError(f"{span} samples complete no whole number of frames of {self.fft_size} every {self.step}")
+        frames = (span - self.fft_size) // self.step + 1
+        est, curve, latest = np.empty(frames), np.empty(self.n_history), ctypes.c_double()
+        _lib.check(_lib.load().frt_pitch_live_push(self._device(), x.ctypes.data, int(x.dtype == np.float64), x.shape[0], span,
+                                                   x.strides[0] // x.itemsize, float(self.min_db), float(self.conf),
+                                                   float(self.p_delta), est.ctypes.data, ctypes.byref(latest), curve.ctypes.data,
+                                                   None))
+        self.pitch, self.curve = latest.value, curve
+        return est
+
+    def estimate_pitch(self, frame: np.ndarray):
+        """frame: [rows, fft_size]: spectrum from row 0, level from every row.  Hz, or nan if unvoiced.  As upstream, the gate's
+        previous estimate moves on; history, pitch and curve belong to update() and stay."""
+        frame = np.asarray(frame)
+        if frame.shape[-1] != self.fft_size:
+            raise ValueError(f"estimate_pitch expects {self.fft_size} samples, got {frame.shape[-1]}")
+        self._device()
+        (_, history), shown = self._device_state(), (self.pitch, self.curve)
+        est = float(self._push(frame)[0])
+        self._set_device_state(np.full(1, est), history)
+        self.pitch, self.curve = shown
+        return est
+
+    def _device_state(self):
+        previous, history = np.empty(1), np.empty(self.n_history)
+        _lib.check(_lib.load().frt_pitch_live_get_state(self._live, previous.ctypes.data, history.ctypes.data))
+        return previous, history
+
+    def _set_device_state(self, previous, history):
+        _lib.check(_lib.load().frt_pitch_live_set_state(self._live, previous.ctypes.data, history.ctypes.data))
+
+    @property
+    def prev_f0(self):
+        previous = self._previous if self._live is None else self._device_state()[0]
+        return None if np.isnan(previous[0]) else float(previous[0])
+
+    @prev_f0.setter
+    def prev_f0(self, value):
+        previous = np.full(1, np.nan if value is None else float(value))
+        if self._live is None:
+            self._previous = previous
+        else:
+            self._set_device_state(previous, self._device_state()[1])
+
+    def get_state(self) -> PitchState:
+        """The PitchState of this one stream (numpy): PitchBatch.run(rest, state=...) continues where the stream stands."""
+        previous, history = (self._previous.copy(), self._history.copy()) if self._live is None else self._device_state()
+        in_ring = self.input_buf.offset - self.next_in_offset
+        tail = np.array(self.input_buf.data_indexed(self.input_buf.offset, in_ring), np.float64)
+        if self._carry is not None:
+            if in_ring and tail.shape[0] != self._carry.shape[0]:
+                raise ValueError(f"a state of {self._carry.shape[0]} rows ahead of a ring of {tail.shape[0]}")
+            tail = np.concatenate([self._carry, tail], axis=1) if in_ring else self._carry.copy()
+        return PitchState(tail[None], tail.shape[1], previous, history[None])
+
+    def set_state(self, state: PitchState) -> None:
+        """Continue from a PitchState of one stream (PitchBatch's, or another stream's): its tail stands ahead of whatever the
+        ring receives from now on; what the ring holds at this moment is not part of the stream."""
+        tail, previous, history = (np.asarray(to_host(v), np.float64) for v in (state.tail, state.previous, state.history))
+        pending = int(state.pending)
+        want = {"tail": (1, tail.shape[1] if tail.ndim == 3 else 0, pending), "previous": (1,), "history": (1, self.n_history)}
+        got = {"tail": tail.shape, "previous": previous.shape, "history": history.shape}
+        if not 0 <= pending < self.fft_size or got != want or tail.shape[1] not in (1, 2):
+            raise ValueError(f"state of another shape: {got} (want {want}, one or two rows), pending {pending} (below {self.fft_size})")
+        self._carry = tail[0].copy() if pending else None
+        self.next_in_offset = self.input_buf.offset
+        self._previous, self._history = previous.copy(), np.ascontiguousarray(history[0])
+        if self._live is not None:
+            self._set_device_state(self._previous, self._history)

@@ -456,6 +456,33 @@ int frt_pitch_refresh(const double* estimates, int streams, int64_t n_frames, co
                       const double* history_in, int64_t history_length, double min_freq, double max_freq, int keep_last,
                       double* history_out, double* pitch_out, double* curve_out);
 
+/* ---- T1 live: the pitch tracker's chain for one stream fed chunk by chunk (PitchTrackerStream) ---------------------------------
+ * A small object on top of a ONE-channel frt_pitch plan (not owned; it must outlive the object and is left on the null stream):
+ * the gate's previous estimate, the last history_length estimates (zeros before the first) and the axis range
+ * [min_freq, max_freq] of the curve live on the device.  frt_pitch_live_push takes the HOST samples that complete
+ * n_frames >= 1 frames — span = fft_size + (n_frames - 1) * hop samples per row, row r at x + r * ld_row, dtype 0 float32 /
+ * 1 float64 (widened exactly), rows 1 or 2 — and runs the chain of frt_pitch_track_rows + frt_pitch_refresh on them: spectrum
+ * and estimate from row 0, the gate's level from every row, the gate with the thresholds given here, then the history shifted
+ * by the new estimates.  estimates_out: [n_frames] (NaN = unvoiced); latest_out: the last of them; curve_out: [history_length],
+ * the curve of frt_pitch_refresh after this push.  One copy back and one synchronisation per push, null stream.  The same
+ * samples give the bits of frt_pitch_track_rows / frt_pitch_refresh however the frames are spread over pushes: up to
+ * `crossover` frames per push (default 16) the strengths come from a kernel with one candidate per lane, above it from the
+ * tiled kernel of frt_pitch_track, with equal bits. */
+typedef struct frt_pitch_live frt_pitch_live;
+int frt_pitch_live_create(frt_pitch_live** h, frt_pitch* plan, int64_t history_length, double min_freq, double max_freq);
+void frt_pitch_live_destroy(frt_pitch_live* h);
+/* no previous estimate, a history of zeros */
+int frt_pitch_live_reset(frt_pitch_live* h);
+int frt_pitch_live_push(frt_pitch_live* h, const void* x, int dtype, int rows, int64_t span, int64_t ld_row, double min_db,
+                        double conf, double p_delta, double* estimates_out, double* latest_out, double* curve_out,
+                        int64_t* n_frames_out);
+/* previous: [1] (NaN = none), history: [history_length]; host or device memory */
+int frt_pitch_live_get_state(frt_pitch_live* h, double* previous, double* history);
+int frt_pitch_live_set_state(frt_pitch_live* h, const double* previous, const double* history);
+/* frames per push (0 .. 1024) up to which the one-candidate-per-lane kernel forms the strengths */
+int frt_pitch_live_set_crossover(frt_pitch_live* h, int frames);
+int frt_pitch_live_crossover(const frt_pitch_live* h);
+
 /* ---- L1: level meters and long-time levels (Levels_Widget, LongLevelWidget) -----------------------------
  * Per channel and per chunk (friture/levels.py:85-124, iec.py, ballistic_peak.py:21-66,
  * signal/exp_smoothing.py:40-56): value_max = max|y| (chunks of length > 0); old_max = value_max if
