@@ -82,10 +82,13 @@ __device__ double block_max(double v, double* red) {
     return s;
 }
 
-// The sub-transform engine: the compile-time plan 6 x 10 x 10 x 10 (fft_static.h) for the default window's 6000 points,
-// the run-time mixed-radix plan for every other 5-smooth length.
-// ST: 0 the run-time plan, 1 the 6000-point plan (R = 2 of the default window), 2 the 3000-point plan 3 x 10 x 10 x 10 (R = 4 of the
-// default window: small batches as launches of their phases — eight forward and four inverse workgroups of 48 KB per pair, three per CU)
+// The sub-transform engine: the compile-time plan 6 x 10 x 10 x 10 (fft_static.h) for the 6000 points of the default window's two-way
+// split, the run-time mixed-radix plan for every other 5-smooth length.
+// ST: 0 the run-time plan, 1 the 6000-point plan, 2 the 3000-point plan 3 x 10 x 10 x 10 (R = 4 of the default window: small batches
+// as launches of their phases — eight forward and four inverse workgroups of 48 KB per pair, three per CU).  ST != 0 exists for the
+// default window alone, as the instances <2, 1> and <4, 2>: a template's R is the split it reads and indexes by, so a handle takes a
+// compile-time plan only where its own R is that instance's (frt_gcc_create).  Windows of 12000 (R = 1) and 48000 samples (R = 4)
+// also have M2 = 6000; they run the run-time plan 4 x 4 x 5 x 5 x 5 x 3 in <1, 0> and <4, 0>.
 constexpr int kGccStaticM2 = 6000, kGccStaticM2Small = 3000;
 constexpr int kGccSlotsMax = (kGccMaxM2 + kGccThreads - 1) / kGccThreads;      // points of a sub-transform per thread: 6
 template <int ST>
@@ -1109,7 +1112,8 @@ struct frt_gcc {
     MixedPlan plan{};
     hipStream_t stream = nullptr;
     DeviceBuffer window, twm, tw2, tws, twl, dw, scratch;
-    int static_plan = 0;                 // 1: M2 = 6000, 2: M2 = 3000 — the compile-time plans of fft_static.h (gcc_fft)
+    int static_plan = 0;                 // the default window (M = 12000) alone: 1 with R = 2 (M2 = 6000), 2 with R = 4 (M2 = 3000) — the
+                                         // compile-time plans of fft_static.h (gcc_fft), whose kernel instances are <2, 1> and <4, 2>
     DeviceBuffer psum;
     DeviceBuffer in0, in1, out, argmax, means, old, sm, stats;
     size_t lds_bytes = 0;
@@ -1219,7 +1223,10 @@ extern "C" int frt_gcc_create(frt_gcc** out, int length, int n_pairs) {
         return FRT_ERR_HIP;
     }
     h->lds_bytes = (size_t)h->M2 * 16 + 16 * sizeof(double) + 16 * sizeof(int);
-    h->static_plan = exp_env("FRT_GCC_NO_STATIC_PLAN") != nullptr ? 0 : h->M2 == kGccStaticM2 ? 1 : (h->M2 == kGccStaticM2Small && small_batch) ? 2 : 0;
+    // M2 alone does not select plan 1: 6000 points are also the whole of a 12000-sample window (R = 1) and a quarter of a 48000-sample
+    // one (R = 4), and the <2, 1> instances read sample pairs 2 m + r and keep the cross spectrum of M <= 12288 bins in registers
+    const bool two_way_default = R == 2 && h->M == 2 * kGccStaticM2;
+    h->static_plan = exp_env("FRT_GCC_NO_STATIC_PLAN") != nullptr ? 0 : two_way_default ? 1 : (h->M2 == kGccStaticM2Small && small_batch) ? 2 : 0;
     if (h->static_plan == 1) rc = upload(h->tws, make_static_twiddles<double>({6, 10, 10, 10}));
     else if (h->static_plan == 2 && !(rc = upload(h->tws, make_static_twiddles<double>({3, 10, 10, 10}))))
         rc = h->psum.reserve((size_t)n_pairs * 2 * 4 * sizeof(double));

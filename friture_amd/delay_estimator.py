@@ -432,8 +432,8 @@ class DelayEstimatorBatch:
     written to.  A recording in pieces equals the whole to rounding.
 
     Not safe to call while another thread creates or calls a GCC-PHAT handle: for the duration of the call run() sets the
-    process-wide option "gcc_one_workgroup" (and "gcc_any_length" while it creates the handles of 12000-sample windows) through
-    frt_set_option and puts the earlier values back afterwards; the other thread would see the forced values."""
+    process-wide option "gcc_one_workgroup" through frt_set_option and puts the earlier value back afterwards; the other thread
+    would see the forced value."""
 
     def __init__(self, delayrange_s: float = DEFAULT_DELAYRANGE):
         t = filter_design.load_tables()
@@ -449,15 +449,9 @@ class DelayEstimatorBatch:
         return delay_schedule(n_samples, self.delayrange_s, chunk, ends, state)
 
     def _plan(self, n_pairs):
-        """The GCC-PHAT handle of a slab size.  Windows of 12000 samples (0.5 s) go through the chirp-z transform: for a half
-        length of 6000 frt_gcc_create takes the compile-time plan of the default window's two sub-transforms of 6000 points, which
-        does not fit this length's single one (gcc.hip is tied to its measured records and is not changed here)."""
+        """The GCC-PHAT handle of a slab size."""
         if n_pairs not in self._gcc:
-            if self.length // 2 == 6000:
-                with _gcc_options(gcc_any_length=1):
-                    self._gcc[n_pairs] = GccPhat(self.length, n_pairs)
-            else:
-                self._gcc[n_pairs] = GccPhat(self.length, n_pairs)
+            self._gcc[n_pairs] = GccPhat(self.length, n_pairs)
         return self._gcc[n_pairs]
 
     def _check_input(self, x, state):

@@ -6,6 +6,8 @@ two-channel stream: the windows are views of the rings and GCC-PHAT's mean remov
 """
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
 from oracle import dsp
@@ -13,7 +15,7 @@ from oracle import dsp
 NDEC, RATE = 2, 12000.0
 
 # name -> (delay range in s, samples, seed, streams); the shapes of the GPU tests
-CASES = {"r0.1": (0.1, 1 << 16, 11, 2), "r0.5": (0.5, 1 << 17, 12, 2), "r1.0": (1.0, 1 << 18, 13, 2)}
+CASES = {"r0.1": (0.1, 1 << 16, 11, 2), "r0.5": (0.5, 1 << 17, 12, 2), "r1.0": (1.0, 1 << 18, 13, 2), "r2.0": (2.0, 1 << 19, 14, 2)}
 # what the reference widget is recorded on: one stream of a case, or its own ragged chunks (multiples of 4, one long push)
 GOLDEN = {"r0.1": ("r0.1", 1, None), "r0.5": ("r0.5", 0, None),
           "ragged": ("r0.1", 0, [512, 1024, 1028, 4100, 4612, 44612, 45124, 60000, 65024, 65536])}
@@ -141,3 +143,12 @@ def replay(x, delayrange, ends, carry=None):
 def doubtful(r, w):
     """A window whose correlation or arg-max the replay itself decides by less than rounding can move."""
     return bool(not r["gated"][w] and (abs(r["pct"][w] - np.round(r["pct"][w])) < 1e-6 or r["margin"][w] < 1e-9))
+
+
+@functools.lru_cache(maxsize=None)
+def case(name, dtype):
+    """(x [S, 2, T] of `dtype`, the replay of every stream of it): computed once per session, never written to."""
+    delayrange, T, _, S = CASES[name]
+    x = signal(name).astype(dtype)
+    x.setflags(write=False)
+    return x, tuple(replay(x[s].astype(np.float64), delayrange, chunk_ends(T)) for s in range(S))

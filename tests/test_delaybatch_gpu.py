@@ -23,13 +23,7 @@ STATE_BAR = 1e-9     # the decimators' end states relative to the stage's max |r
 FIELDS = ("delay_ms", "distance_m", "extremum")
 
 
-@functools.lru_cache(maxsize=None)
-def case(name, dtype):
-    """(x [S, 2, T] of `dtype`, the replay of every stream of it): computed once, never written to."""
-    delayrange, T, _, S = H.CASES[name]
-    x = H.signal(name).astype(dtype)
-    x.setflags(write=False)
-    return x, tuple(H.replay(x[s].astype(np.float64), delayrange, H.chunk_ends(T)) for s in range(S))
+case = H.case        # (x [S, 2, T] of a dtype, the replay of every stream of it): shared with tests/test_gcc_gpu.py
 
 
 def host(v):
@@ -71,7 +65,7 @@ def test_batch_against_replay(hip, name, dtype, kind):
     batch = DelayEstimatorBatch(delayrange)
     res = batch.run(xin, keep="all", with_xcorr=True)
     assert isinstance(res.delay_ms, np.ndarray) == (kind == "numpy") and isinstance(res.state.smoothed, np.ndarray) == (kind == "numpy")
-    assert len(res.window_end) == {"r0.1": 13, "r0.5": 5, "r1.0": 5}[name]
+    assert len(res.window_end) == {"r0.1": 13, "r0.5": 5, "r1.0": 5, "r2.0": 5}[name]
     assert np.array_equal(res.window_end, refs[0]["window_end"]) and np.array_equal(res.refresh_chunk, np.unique(refs[0]["window_chunk"]))
     worst = worst_of(res, refs, name)
     for s, r in enumerate(refs):                                     # what the widget shows after the chunks that completed a window
@@ -207,7 +201,7 @@ def test_slabs_do_not_change_a_bit(hip):
         assert np.array_equal(one.state.smoothed, other.state.smoothed) and np.array_equal(one.state.means, other.state.means)
 
 
-@pytest.mark.parametrize("name", ["r0.1", "r1.0"])
+@pytest.mark.parametrize("name", list(H.CASES))
 def test_refreshes_equal_the_stream_object(hip, name):
     delayrange, T = H.CASES[name][:2]
     x = np.array(case(name, np.float64)[0][0])

@@ -2,13 +2,19 @@
 
 float64 on both sides with a different FFT factorisation: max|xcorr - ref| / max|ref| <= 1e-9 (the
 north_star bar is 1e-5), identical argmax."""
+import functools
+
 import numpy as np
 import pytest
 
 from conftest import rel_max
 from oracle import dsp
 
+import delaybatch_replay as H
+
 pytestmark = pytest.mark.gpu
+
+BAR = 1e-9           # the delay-batch tests' bar for read-outs, relative to max(|ref|, 1) (tests/test_delaybatch_gpu.py)
 
 
 def f64(x):
@@ -460,3 +466,90 @@ def test_gcc_resident_kernel_on_windows_that_are_views(hip, option):
     assert v0.data_ptr() % 16 == 8
     x_un, am_un = g.correlate(v0, v1)
     assert torch.equal(x_un, x_al) and list(am_un.cpu().numpy()) == list(am_al.cpu().numpy()) == [21] * P
+
+
+@functools.lru_cache(maxsize=None)
+def plan_class_case(L):
+    """Three pairs of L samples with a lag of 41 and their oracle correlations: plain noise; the same with a DC offset of 2.5 on one
+    signal and -6.5 on the other; inverted polarity.  Computed once per length, never written to."""
+    rng = np.random.default_rng(L)
+    d0 = 0.25 * rng.standard_normal((3, L))
+    d1 = np.roll(d0, 41, axis=1) + 0.02 * rng.standard_normal((3, L))
+    d0[1] += 2.5
+    d1[1] -= 6.5
+    d1[2] = -d1[2]
+    refs = np.stack([dsp.gcc_phat(d0[p].copy(), d1[p].copy())[0] for p in range(3)])
+    for a in (d0, d1, refs):
+        a.setflags(write=False)
+    return d0, d1, refs
+
+
+@pytest.mark.parametrize("one_workgroup", [-1, 0, 1])
+@pytest.mark.parametrize("L", [9600, 12000, 12288, 21600, 24000, 24576, 43200, 48000, 49152])
+def test_gcc_every_plan_class_and_dispatch(hip, option, L, one_workgroup):
+    """frt_gcc_create picks a split R = 1 / 2 / 4 by the half length M = L / 2 and, apart from it, a compile-time plan for the
+    sub-transforms; the kernel instances of a compile-time plan are compiled for ONE split.  Per split: a run-time length, the length
+    whose sub-transforms have the compile-time plan's 6000 points (12000 and 48000 samples — delay ranges of 0.5 s and 2 s — beside the
+    default window's 24000), and the LDS-limit length of 6144 points; each through the shape rule, the launches of phases and the
+    one-workgroup kernel (create-time selection reads the option).  The last pair and the last samples count: with the 6000-point
+    plan's two-way instances a 12000-sample window was read up to twice its length."""
+    from friture_amd.signal.correlation import GccPhat
+    option("gcc_one_workgroup", one_workgroup)
+    d0, d1, refs = plan_class_case(L)
+    x, am = GccPhat(L, 3).correlate(d0.copy(), d1.copy())
+    worst = max(rel_max(x[p], refs[p]) for p in range(3))
+    print(f"L {L} gcc_one_workgroup {one_workgroup}: worst {worst:.3e} (bar 1e-9)")
+    for p in range(3):
+        assert rel_max(x[p], refs[p]) <= 1e-9, (L, p, rel_max(x[p], refs[p]))
+        assert am[p] == int(np.argmax(np.abs(refs[p]))) == 41
+    assert x[0, 41] > 0 and x[1, 41] > 0 and x[2, 41] < 0
+
+
+def test_gcc_spin_box_ranges(request):
+    """The windows of the delay-range spin box's values from 0.1 to 1.0 s in its one decimal, and of 2.0 s, one click up from the
+    default: every plan class that create-time selection has among them (run-time plans with R = 1 / 2 / 4, chirp-z for 16800, the
+    6000-point sub-transforms of 12000, 24000 and 48000), default dispatch."""
+    from friture_amd.delay_estimator import delay_lengths
+    from friture_amd.signal.correlation import GccPhat
+    lengths = [delay_lengths(round(0.1 * i, 1))[0] for i in range(1, 11)] + [delay_lengths(2.0)[0]]
+    assert all(L % 2 == 0 for L in lengths) and {12000, 24000, 48000} <= set(lengths)
+    request.getfixturevalue("hip")
+    for L in lengths:
+        rng = np.random.default_rng(L + 1)
+        d0 = 0.25 * rng.standard_normal((2, L))
+        d1 = np.roll(d0, 41, axis=1) + 0.02 * rng.standard_normal((2, L))
+        d1[1] = -d1[1]
+        refs = [dsp.gcc_phat(d0[p].copy(), d1[p].copy())[0] for p in range(2)]
+        x, am = GccPhat(L, 2).correlate(d0.copy(), d1.copy())
+        print(f"L {L}: worst {max(rel_max(x[p], refs[p]) for p in range(2)):.3e} (bar 1e-9)")
+        for p in range(2):
+            assert rel_max(x[p], refs[p]) <= 1e-9, (L, p, rel_max(x[p], refs[p]))
+            assert am[p] == int(np.argmax(np.abs(refs[p]))) == 41
+        assert x[1, 41] < 0 < x[0, 41]
+
+
+@pytest.mark.parametrize("name", ["r0.5", "r2.0"])
+def test_delay_widgets_at_half_a_second_and_two_seconds(hip, name):
+    """DelayEstimator and DelayEstimatorStream with windows of 12000 and 48000 samples, fed stream 0 of the delay-batch case in
+    512-sample chunks, against the numpy replay of the widget (tests/delaybatch_replay.py; on the CPU it equals the reference
+    widget's recorded read-outs bit for bit, tests/test_delaybatch_cpu.py): the read-out after every chunk."""
+    from friture_amd.delay_estimator import DelayEstimator, DelayEstimatorStream
+    delayrange, T = H.CASES[name][:2]
+    x, refs = H.case(name, np.float64)
+    x, r = x[0], refs[0]
+    shown, window_chunk = r["shown"], r["window_chunk"]
+    assert len(window_chunk) >= 5 and not r["gated"].any()
+    # the window a chunk's read-out comes from (-1: none yet), and whether the replay itself decides it by less than rounding can move
+    last_window = np.searchsorted(window_chunk, np.arange(len(shown)), side="right") - 1
+    unsure = np.array([w >= 0 and H.doubtful(r, w) for w in last_window])
+    for kind in (DelayEstimator, DelayEstimatorStream):
+        est = kind(delayrange)
+        worst = 0.0
+        for c in range(T // 512):
+            est.handle_new_data(np.array(x[:, c * 512:(c + 1) * 512]))
+            got = (est.delay_ms, est.distance_m, est.Xcorr_extremum)
+            worst = max(worst, max(abs(g - ref) / max(abs(ref), 1.0) for g, ref in zip(got, shown[c, :3])))
+            if not unsure[c]:
+                assert est.correlation == shown[c, 3], (kind.__name__, c, est.correlation, shown[c, 3])
+        print(f"{name} {kind.__name__}: worst {worst:.3e} (bar {BAR})")
+        assert worst <= BAR
