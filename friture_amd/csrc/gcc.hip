@@ -1109,6 +1109,7 @@ using namespace frt;
 
 struct frt_gcc {
     int L = 0, M = 0, M2 = 0, R = 1, n_pairs = 0;
+    int one_workgroup = -1;              // >= 0: this handle's own value of "gcc_one_workgroup"; -1: the process option's (one_workgroup_of)
     MixedPlan plan{};
     hipStream_t stream = nullptr;
     DeviceBuffer window, twm, tw2, tws, twl, dw, scratch;
@@ -1123,6 +1124,9 @@ struct frt_gcc {
     DeviceBuffer chirp, bhat, work, spec, twr, twc, gmax, part_val, part_idx, prof;
 };
 
+// "gcc_one_workgroup" as handle h sees it: its own value where it was made with one (frt_gcc_create_fixed), else the process option
+static int one_workgroup_of(const frt_gcc* h) { return h->one_workgroup >= 0 ? h->one_workgroup : option(kOptGccOneWorkgroup); }
+
 extern "C" void frt_gcc_destroy(frt_gcc* h) {
     if (!h) return;
     free_retired_allocations(true);      // blocks parked by growing buffers (common.h); synchronises the device like the releases below
@@ -1133,12 +1137,14 @@ extern "C" void frt_gcc_destroy(frt_gcc* h) {
     delete h;
 }
 
-extern "C" int frt_gcc_create(frt_gcc** out, int length, int n_pairs) {
+extern "C" int frt_gcc_create_fixed(frt_gcc** out, int length, int n_pairs, int one_workgroup) {
     FRT_REQUIRE(out, "frt_gcc_create: null handle pointer");
     *out = nullptr;
     FRT_REQUIRE(length >= 4 && length % 2 == 0, "frt_gcc_create: length %d must be even and >= 4", length);
     FRT_REQUIRE(n_pairs >= 1, "frt_gcc_create: n_pairs %d < 1", n_pairs);
+    FRT_REQUIRE(one_workgroup >= -1 && one_workgroup <= 1, "frt_gcc_create_fixed: one_workgroup %d is not -1, 0 or 1", one_workgroup);
     frt_gcc* h = new frt_gcc();
+    h->one_workgroup = one_workgroup;
     h->L = length;
     h->M = length / 2;
     h->n_pairs = n_pairs;
@@ -1153,7 +1159,7 @@ extern "C" int frt_gcc_create(frt_gcc** out, int length, int n_pairs) {
     // per pair side by side.  Measured (profiles/r05_gcc_batch.txt): 1 pair 47.5 -> 35.1 us, 4: 50.1 -> 36.7, 16: 58.1 -> 45.8,
     // 32: 62.6 -> 56.7; beyond that the quarter-strided loads and stores of the four-way split cost more than its width buys
     // (64 pairs 72 -> 80 us, 100: 84 -> 114) and the two-way split stays.
-    const bool small_batch = h->M == 2 * kGccStaticM2 && (long long)n_pairs * 8 <= (long long)device_cu_count() && option(kOptGccOneWorkgroup) <= 0 &&
+    const bool small_batch = h->M == 2 * kGccStaticM2 && (long long)n_pairs * 8 <= (long long)device_cu_count() && one_workgroup_of(h) <= 0 &&
                              exp_env("FRT_GCC_NO_STATIC_PLAN") == nullptr && exp_env("FRT_GCC_NO_SMALL_PLAN") == nullptr;
     if (small_batch && R == 2) R = 4;
     h->R = R;
@@ -1255,6 +1261,8 @@ extern "C" int frt_gcc_create(frt_gcc** out, int length, int n_pairs) {
     return FRT_OK;
 }
 
+extern "C" int frt_gcc_create(frt_gcc** out, int length, int n_pairs) { return frt_gcc_create_fixed(out, length, n_pairs, -1); }
+
 extern "C" int frt_gcc_set_stream(frt_gcc* h, void* s) {
     FRT_REQUIRE(h, "frt_gcc_set_stream: null handle");
     h->stream = (hipStream_t)s;
@@ -1335,7 +1343,7 @@ extern "C" int frt_gcc_phat(frt_gcc* h, const double* d0, const double* d1, doub
     a.vec = ((uintptr_t)a.d0 % 16 == 0) && ((uintptr_t)a.d1 % 16 == 0) && ((uintptr_t)a.xcorr % 16 == 0);
     const int st = h->static_plan;
     a.psum = st == 2 ? h->psum.as<double>() : nullptr;
-    const int force = option(kOptGccOneWorkgroup);
+    const int force = one_workgroup_of(h);
     // the default window, one workgroup per pair: nothing passes through HBM between the signals and the correlation (gcc_resident.h)
     const bool can_reside = st == 1 && h->R == 2 && option(kOptGccResident) != 0;
     // A pair as launches of its own phases while the batch leaves most CUs idle: below a sixth of a workgroup per CU when the

@@ -8,7 +8,6 @@ correlation, peak pick and the delay / polarity / confidence read-out (frt_gcc_r
 """
 from __future__ import annotations
 
-from contextlib import contextmanager
 from typing import NamedTuple
 
 import numpy as np
@@ -360,20 +359,6 @@ def delay_schedule(n_samples, delayrange_s=DEFAULT_DELAYRANGE, chunk=512, ends=N
                          np.array(runs, np.int64).reshape(-1, DELAY_RUNS, 4), out, length, needed, tail, r.offset - offset0)
 
 
-@contextmanager
-def _gcc_options(**values):
-    """frt_set_option for the duration of a block; the earlier values come back."""
-    from . import _lib
-    before = {name: _lib.get_option(name) for name in values}
-    for name, value in values.items():
-        _lib.set_option(name, value)
-    try:
-        yield
-    finally:
-        for name, value in before.items():
-            _lib.set_option(name, value)
-
-
 class DelayState(NamedTuple):
     """What a delay estimator carries between two calls."""
     zi: object                  # [S, 2, Ndec, 12] float64: the decimators' DF2T states, decimate_multiple's order
@@ -429,11 +414,8 @@ class DelayEstimatorBatch:
 
     The correlations of all windows ([S, W, L] float64) are held on the device whether with_xcorr asks for them or not; the
     effective windows go to GCC-PHAT in slabs of pairs that fit scratch_bytes (a pair at least).  The caller's state is never
-    written to.  A recording in pieces equals the whole to rounding.
-
-    Not safe to call while another thread creates or calls a GCC-PHAT handle: for the duration of the call run() sets the
-    process-wide option "gcc_one_workgroup" through frt_set_option and puts the earlier value back afterwards; the other thread
-    would see the forced value."""
+    written to.  A recording in pieces equals the whole to rounding.  The GCC-PHAT handles are pinned to one workgroup per pair,
+    so that a pair's bits do not depend on the slab size."""
 
     def __init__(self, delayrange_s: float = DEFAULT_DELAYRANGE):
         t = filter_design.load_tables()
@@ -449,9 +431,10 @@ class DelayEstimatorBatch:
         return delay_schedule(n_samples, self.delayrange_s, chunk, ends, state)
 
     def _plan(self, n_pairs):
-        """The GCC-PHAT handle of a slab size."""
+        """The GCC-PHAT handle of a slab size: one workgroup per pair whatever the slab's size, so that a pair's bits do not
+        depend on how many ride along."""
         if n_pairs not in self._gcc:
-            self._gcc[n_pairs] = GccPhat(self.length, n_pairs)
+            self._gcc[n_pairs] = GccPhat(self.length, n_pairs, one_workgroup=True)
         return self._gcc[n_pairs]
 
     def _check_input(self, x, state):
@@ -511,14 +494,12 @@ class DelayEstimatorBatch:
                 per = int(min(S * W, 65535, max(1, int(scratch_bytes) // (2 * L * 8))))
                 runs = np.ascontiguousarray(plan.runs, np.int64)
                 slabs = ctypes.c_int(0)
-                # one workgroup per pair whatever the slab's size: a pair's bits then do not depend on how many ride along
-                with _gcc_options(gcc_one_workgroup=1):
-                    full, last = self._plan(per), self._plan((S * W) % per or per)
-                    for g in (full, last):
-                        _lib.check(lib.frt_gcc_set_stream(g._h, None))
-                    _lib.check(lib.frt_delaybatch_windows(
-                        vp(dec.data_ptr()), n_all, n_all, S, L, W, runs.ctypes.data_as(IP), vp(means_in.data_ptr()), full._h, per, last._h,
-                        vp(xcorr.data_ptr()), vp(means.data_ptr()), vp(gated.data_ptr()), ctypes.byref(slabs)))
+                full, last = self._plan(per), self._plan((S * W) % per or per)
+                for g in (full, last):
+                    _lib.check(lib.frt_gcc_set_stream(g._h, None))
+                _lib.check(lib.frt_delaybatch_windows(
+                    vp(dec.data_ptr()), n_all, n_all, S, L, W, runs.ctypes.data_as(IP), vp(means_in.data_ptr()), full._h, per, last._h,
+                    vp(xcorr.data_ptr()), vp(means.data_ptr()), vp(gated.data_ptr()), ctypes.byref(slabs)))
                 self.last_slabs = slabs.value
             _lib.check(lib.frt_delaybatch_readout(
                 vp(xcorr.data_ptr()), vp(gated.data_ptr()), S, W, L, vp(sm_in.data_ptr()), vp(present_in.data_ptr()), 0.3,

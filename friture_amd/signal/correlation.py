@@ -51,13 +51,18 @@ def generalized_cross_correlation(d0, d1):
 
 
 class GccPhat:
-    """Batched GCC-PHAT + read-out over `n_pairs` windows of `length` samples."""
+    """Batched GCC-PHAT + read-out over `n_pairs` windows of `length` samples.  one_workgroup: True / False pin the handle to
+    one workgroup per pair / to a pair as launches of its phases whatever the process option "gcc_one_workgroup" says; None
+    leaves it to the batch size and that option."""
 
-    def __init__(self, length: int, n_pairs: int = 1):
+    def __init__(self, length: int, n_pairs: int = 1, one_workgroup=None):
         self._lib = _lib.init()
         self.length, self.n_pairs = length, n_pairs
         self._h = ctypes.c_void_p()
-        _lib.check(self._lib.frt_gcc_create(ctypes.byref(self._h), length, n_pairs))
+        if one_workgroup is None:
+            _lib.check(self._lib.frt_gcc_create(ctypes.byref(self._h), length, n_pairs))
+        else:
+            _lib.check(self._lib.frt_gcc_create_fixed(ctypes.byref(self._h), length, n_pairs, int(bool(one_workgroup))))
 
     def __del__(self):
         try:

@@ -51,7 +51,9 @@ int frt_is_device_pointer(const void* p);
  *   "gcc_one_workgroup"    frt_gcc_phat: 1 = one workgroup per window pair whatever the batch size, 0 = a pair as launches
  *                          of its phases (default: by batch size)
  *                          (also read by frt_gcc_create: a handle of at most CUs / 8 pairs of the default window made while the
- *                          option is 1 gets the two-way plan of the large batches instead of the four-way plan of the small ones)
+ *                          option is 1 gets the two-way plan of the large batches instead of the four-way plan of the small ones;
+ *                          a handle made by frt_gcc_create_fixed with one_workgroup >= 0 uses that value in both places for its
+ *                          whole life and never reads this option)
  *   "gcc_resident"         frt_gcc_phat, default window (24000 samples), one workgroup per pair: 0 = the kernel that parks the
  *                          sub-spectra in a scratch slab in HBM instead of the one that keeps them in registers and LDS
  *   "ola_defer"            frt_octbank_filter / _energies (mode 1, batched, >= 6 bands per octave): 0 = every stage's band filters in the
@@ -283,6 +285,8 @@ int frt_specgram_reset(frt_specgram* h);
  * that side effect. */
 typedef struct frt_gcc frt_gcc;
 int frt_gcc_create(frt_gcc** h, int length, int n_pairs);
+/* The same with the handle's own value of "gcc_one_workgroup": 1 or 0 pins it, -1 leaves it to the process option (frt_gcc_create). */
+int frt_gcc_create_fixed(frt_gcc** h, int length, int n_pairs, int one_workgroup);
 void frt_gcc_destroy(frt_gcc* h);
 int frt_gcc_set_stream(frt_gcc* h, void* hip_stream);
 /* d0, d1, xcorr_out: [n_pairs][length] doubles; argmax_out: [n_pairs] index of max |xcorr| or NULL;

@@ -1,5 +1,5 @@
 """The delay estimator widget replayed in numpy from oracle.dsp as it stands (decimate_multiple, MirrorRing, gcc_phat,
-delay_readout), and the seeded cases that the delay-batch tests and tools/record_delaybatch_golden.py share.  Not a test module.
+delay_readout), and the seeded cases that the delay-batch tests and oracle/golden_delaybatch.py share.
 
 replay() does what Delay_Estimator_Widget.handle_new_data does (friture/delay_estimator.py:87-176) chunk by chunk on one
 two-channel stream: the windows are views of the rings and GCC-PHAT's mean removal is written back into them.
@@ -10,7 +10,8 @@ import functools
 
 import numpy as np
 
-from oracle import dsp
+from . import dsp
+from .cases import chunk_ends
 
 NDEC, RATE = 2, 12000.0
 
@@ -29,28 +30,6 @@ def golden_ends(name):
     return chunk_ends(CASES[case][1]) if ends is None else np.array(ends, np.int64)
 
 
-def golden_layout():
-    """[(key, length)] of the arrays in tests/golden/delaybatch.npy, one float64 vector: per case of GOLDEN the four read-outs
-    after every chunk, then the final old_Xcorr.  (An .npz under tests/golden/ belongs to the recorders of oracle/make_golden.py;
-    until this one is among them the fixture is a plain array.)"""
-    out = []
-    for name, (case, _, _) in GOLDEN.items():
-        out += [(f"{name}_{column}", len(golden_ends(name))) for column in COLUMNS]
-        out.append((f"{name}_old_Xcorr", int(2 * CASES[case][0] * RATE)))
-    return out
-
-
-def golden_pack(arrays):
-    return np.concatenate([np.asarray(arrays[key], np.float64).reshape(n) for key, n in golden_layout()])
-
-
-def golden_unpack(vector):
-    layout = golden_layout()
-    assert vector.dtype == np.float64 and vector.shape == (sum(n for _, n in layout),)
-    edges = np.cumsum([0] + [n for _, n in layout])
-    return {key: vector[a:b] for (key, _), a, b in zip(layout, edges[:-1], edges[1:])}
-
-
 def signal(name):
     """[S, 2, T] float64: seeded noise with a DC offset of 0.01; channel 1 is channel 0 rolled by 4 * 31 samples plus 1 % noise;
     the last stream's channel 1 has a stretch of exact zeros long enough to gate windows."""
@@ -65,10 +44,6 @@ def signal(name):
     # zeros (their tails take thousands of samples per decade to die), so these are the windows that the reference gates
     x[S - 1, 1, :4 * 3 * int(0.5 * int(2 * delayrange * RATE))] = 0.0
     return x
-
-
-def chunk_ends(T, chunk=512):
-    return np.minimum(np.arange(1, -(-T // chunk) + 1, dtype=np.int64) * chunk, T)
 
 
 def ends_with_cut(T, cut, chunk=512):

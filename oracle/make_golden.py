@@ -39,6 +39,7 @@ RECORDERS = {       # module -> the fixtures it records
     "golden_spectrogrambatch": ("spectrogrambatch",),
     "golden_pitchbatch": ("pitchbatch",),
     "golden_octavespectrumbatch": ("octavespectrumbatch",),
+    "golden_delaybatch": ("delaybatch",),
     "golden_tables": ("filter_tables",),
 }
 

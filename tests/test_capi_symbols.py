@@ -65,3 +65,18 @@ def test_path_selection_options_need_no_gpu_and_reject_unknown_names(lib):
     with pytest.raises(_lib.FritureHipError) as err:
         _lib.set_option("FRT_EDGE_SCALE", 0)
     assert err.value.status == -1 and "unknown option" in str(err.value)
+
+
+def test_gcc_create_fixed_rejects_a_value_outside_its_three(lib):
+    """frt_gcc_create_fixed's one_workgroup is -1, 0 or 1; anything else is FRT_ERR_INVALID with a message, before any device call."""
+    import ctypes
+
+    from friture_amd import _lib
+    for bad in (2, -2):
+        h = ctypes.c_void_p()
+        rc = lib.frt_gcc_create_fixed(ctypes.byref(h), 2400, 1, bad)
+        assert rc == -1 and h.value is None
+        assert b"frt_gcc_create_fixed" in lib.frt_last_error() and b"one_workgroup" in lib.frt_last_error()
+        with pytest.raises(_lib.FritureHipError) as err:
+            _lib.check(rc)
+        assert err.value.status == -1 and f"one_workgroup {bad}" in str(err.value)

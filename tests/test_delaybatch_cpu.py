@@ -1,13 +1,11 @@
 """DelayEstimatorBatch without a GPU: delay_schedule's run table against oracle.dsp.MirrorRing, the numpy replay of the widget
-(tests/delaybatch_replay.py) against the reference widget's recorded read-outs, and the input checks."""
+(oracle/delaybatch.py) against the reference widget's recorded read-outs, and the input checks."""
 import numpy as np
 import pytest
 
 from friture_amd.delay_estimator import DelayEstimatorBatch, DelayRing, delay_lengths, delay_schedule
+from oracle import delaybatch as H
 from oracle import dsp
-
-import delaybatch_replay as H
-from conftest import GOLDEN
 
 
 def mark(k):
@@ -153,10 +151,10 @@ def test_batch_refuses_a_state_of_another_shape():
 
 
 @pytest.mark.parametrize("name", list(H.GOLDEN))
-def test_replay_equals_the_reference_widget(name):
+def test_replay_equals_the_reference_widget(golden, name):
     """The numpy replay is built from pieces that tests/test_oracle_golden.py holds to the reference bit for bit (decimation,
     ring, gcc_phat), so it equals the widget's recorded read-outs bit for bit."""
-    g = H.golden_unpack(np.load(GOLDEN / "delaybatch.npy", allow_pickle=False))
+    g = golden("delaybatch")
     case, stream, _ = H.GOLDEN[name]
     r = H.replay(H.signal(case)[stream], H.CASES[case][0], H.golden_ends(name))
     for k, column in enumerate(H.COLUMNS):

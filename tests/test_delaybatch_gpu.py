@@ -1,4 +1,4 @@
-"""DelayEstimatorBatch on the GPU against the numpy replay of the widget (tests/delaybatch_replay.py), against
+"""DelayEstimatorBatch on the GPU against the numpy replay of the widget (oracle/delaybatch.py), against
 DelayEstimatorStream, and against itself (pieces, slabs, keep); frt_delaybatch_decimate alone against oracle.dsp.
 
 The rounding bars were measured on an MI355X against the replay ("P5"): the next power of ten at or above ten
@@ -11,9 +11,8 @@ import numpy as np
 import pytest
 
 from friture_amd.delay_estimator import DelayEstimatorBatch, DelayEstimatorStream, delay_schedule
+from oracle import delaybatch as H
 from oracle import dsp
-
-import delaybatch_replay as H
 
 pytestmark = pytest.mark.gpu
 
@@ -199,6 +198,29 @@ def test_slabs_do_not_change_a_bit(hip):
         for k in FIELDS + ("correlation", "gated", "argmax", "xcorr", "shown_extremum"):
             assert np.array_equal(getattr(one, k), getattr(other, k)), k
         assert np.array_equal(one.state.smoothed, other.state.smoothed) and np.array_equal(one.state.means, other.state.means)
+
+
+def test_run_leaves_the_process_option_alone_and_is_unmoved_by_it(hip, monkeypatch, option):
+    """The batch's GCC-PHAT handles carry their own dispatch: run() neither sets nor reads "gcc_one_workgroup", and a run while
+    the option forces the launches of phases equals one at the shape rule bit for bit."""
+    from friture_amd import _lib
+
+    def refuse(*args):
+        raise AssertionError("DelayEstimatorBatch.run touched a process option")
+    x = np.array(case("r0.1", np.float32)[0])
+    batch = DelayEstimatorBatch(0.1)
+    with monkeypatch.context() as m:
+        m.setattr(_lib, "set_option", refuse)
+        m.setattr(_lib, "get_option", refuse)
+        first = batch.run(x, keep="all", with_xcorr=True)
+    assert _lib.get_option("gcc_one_workgroup") == -1
+    option("gcc_one_workgroup", 0)
+    for other in (batch, DelayEstimatorBatch(0.1)):                  # handles made before the option was forced, and after
+        second = other.run(x, keep="all", with_xcorr=True)
+        assert _lib.get_option("gcc_one_workgroup") == 0
+        for k in ("xcorr",) + FIELDS + ("correlation", "gated", "argmax"):
+            assert np.array_equal(getattr(first, k), getattr(second, k)), k
+        assert np.array_equal(first.state.smoothed, second.state.smoothed) and np.array_equal(first.state.means, second.state.means)
 
 
 @pytest.mark.parametrize("name", list(H.CASES))

@@ -8,9 +8,9 @@ import numpy as np
 import pytest
 
 from conftest import rel_max
+from oracle import delaybatch as H
 from oracle import dsp
 
-import delaybatch_replay as H
 
 pytestmark = pytest.mark.gpu
 
@@ -505,6 +505,58 @@ def test_gcc_every_plan_class_and_dispatch(hip, option, L, one_workgroup):
     assert x[0, 41] > 0 and x[1, 41] > 0 and x[2, 41] < 0
 
 
+@functools.lru_cache(maxsize=None)
+def pinned_case(L, n):
+    """n pairs of L samples: noise with a mean of 0.5, the second signal rolled by 13 samples.  Computed once, never written to."""
+    rng = np.random.default_rng(L + n)
+    d0 = 0.25 * rng.standard_normal((n, L)) + 0.5
+    d1 = np.roll(d0, 13, axis=1) + 0.03 * rng.standard_normal((n, L))
+    for a in (d0, d1):
+        a.setflags(write=False)
+    return d0, d1
+
+
+@pytest.fixture
+def option_back_at_rule():
+    """Named before `option` in a test's arguments, so it ends after it: the process option reads -1 once `option` has put it back."""
+    yield
+    from friture_amd import _lib
+    assert _lib.get_option("gcc_one_workgroup") == -1
+
+
+@pytest.mark.parametrize("pin", [True, False])
+@pytest.mark.parametrize("L,n", [(24000, 1), (24000, 40), (2400, 3)])
+def test_gcc_pinned_handle_equals_a_forced_one(hip, option, L, n, pin):
+    """GccPhat(one_workgroup=...) made while the process option is at its shape rule, against a plain handle made and run with the
+    option forced to the same value, bit for bit: the default window in a small batch (the one shape where frt_gcc_create's plan
+    depends on the value), the same above CUs / 8 pairs (only frt_gcc_phat's dispatch is decided) and a run-time plan."""
+    from friture_amd import _lib
+    from friture_amd.signal.correlation import GccPhat
+    d0, d1 = pinned_case(L, n)
+    assert _lib.get_option("gcc_one_workgroup") == -1
+    x_pin, am_pin = GccPhat(L, n, one_workgroup=pin).correlate(d0.copy(), d1.copy())
+    option("gcc_one_workgroup", int(pin))
+    x_forced, am_forced = GccPhat(L, n).correlate(d0.copy(), d1.copy())
+    assert np.array_equal(x_pin, x_forced) and np.array_equal(am_pin, am_forced)
+    assert list(am_pin) == [13] * n
+
+
+@pytest.mark.parametrize("L,n", [(24000, 1), (2400, 3)])
+def test_gcc_pinned_handle_ignores_the_process_option(hip, option_back_at_rule, option, L, n):
+    from friture_amd import _lib
+    from friture_amd.signal.correlation import GccPhat
+    d0, d1 = pinned_case(L, n)
+    g = GccPhat(L, n, one_workgroup=True)
+    assert _lib.get_option("gcc_one_workgroup") == -1
+    x_rule, am_rule = g.correlate(d0.copy(), d1.copy())
+    option("gcc_one_workgroup", 0)
+    assert _lib.get_option("gcc_one_workgroup") == 0
+    x_zero, am_zero = g.correlate(d0.copy(), d1.copy())
+    assert _lib.get_option("gcc_one_workgroup") == 0
+    assert np.array_equal(x_rule, x_zero) and np.array_equal(am_rule, am_zero)
+    assert list(am_rule) == [13] * n
+
+
 def test_gcc_spin_box_ranges(request):
     """The windows of the delay-range spin box's values from 0.1 to 1.0 s in its one decimal, and of 2.0 s, one click up from the
     default: every plan class that create-time selection has among them (run-time plans with R = 1 / 2 / 4, chirp-z for 16800, the
@@ -531,7 +583,7 @@ def test_gcc_spin_box_ranges(request):
 @pytest.mark.parametrize("name", ["r0.5", "r2.0"])
 def test_delay_widgets_at_half_a_second_and_two_seconds(hip, name):
     """DelayEstimator and DelayEstimatorStream with windows of 12000 and 48000 samples, fed stream 0 of the delay-batch case in
-    512-sample chunks, against the numpy replay of the widget (tests/delaybatch_replay.py; on the CPU it equals the reference
+    512-sample chunks, against the numpy replay of the widget (oracle/delaybatch.py; on the CPU it equals the reference
     widget's recorded read-outs bit for bit, tests/test_delaybatch_cpu.py): the read-out after every chunk."""
     from friture_amd.delay_estimator import DelayEstimator, DelayEstimatorStream
     delayrange, T = H.CASES[name][:2]

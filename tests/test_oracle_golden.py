@@ -207,6 +207,6 @@ def test_committed_fixtures_are_what_the_reference_records():
         with np.load(p, allow_pickle=False) as z:
             want[name] = want.get(name, 0) + len(z.files)
     want["filter_tables"] = len((root / "tests" / "golden" / "filter_tables.sha256").read_text().splitlines())
-    assert len(want) >= 17 and want["spectrogrambatch"] > 0 and all(want.values())
-    assert {"pitchbatch", "octavespectrumbatch"} <= set(compared)
+    assert len(want) >= 18 and want["spectrogrambatch"] > 0 and all(want.values())
+    assert {"pitchbatch", "octavespectrumbatch", "delaybatch"} <= set(compared)
     assert compared == want, run.stdout
