@@ -119,6 +119,60 @@ struct DeviceBuffer {
     T* as() const { return reinterpret_cast<T*>(ptr); }
 };
 
+// A grow-only page-locked host block: the staging of every handle that accepts host arrays.  Two rules for its users: a site
+// allocates the byte count it chose (`alloc`: most double their need, some must not), and whatever has to precede a
+// reallocation — synchronising the stream that may still use the block, dropping captured graphs that carry its address —
+// is done by the site, inside `if (buf.grows(need)) { ... }`, before reserve().  A failed allocation leaves an empty buffer.
+struct PinnedBuffer {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    bool grows(size_t need) const { return need > bytes; }
+    int reserve(size_t need, size_t alloc) {
+        if (need <= bytes) return FRT_OK;
+        if (ptr) (void)hipHostFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+        FRT_HIP_CHECK(hipHostMalloc(&ptr, alloc, hipHostMallocDefault));
+        bytes = alloc;
+        return FRT_OK;
+    }
+    int reserve(size_t need) { return reserve(need, 2 * need); }
+    void release() {
+        if (ptr) (void)hipHostFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+    }
+    template <typename T>
+    T* as() const { return reinterpret_cast<T*>(ptr); }
+};
+
+// A PinnedBuffer that an asynchronous copy (or a kernel reading it in place) may still be using when the next call wants
+// it: mark() after enqueueing the use, wait() before touching the block again.
+struct PinnedSlot : PinnedBuffer {
+    hipEvent_t done = nullptr;
+    bool pending = false;
+    int wait() {
+        if (!pending) return FRT_OK;
+        FRT_HIP_CHECK(hipEventSynchronize(done));
+        pending = false;
+        return FRT_OK;
+    }
+    int mark(hipStream_t stream) {
+        if (!done) FRT_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        FRT_HIP_CHECK(hipEventRecord(done, stream));
+        pending = true;
+        return FRT_OK;
+    }
+    void forget() { pending = false; }      // the caller has synchronised the stream itself
+    void release() {
+        if (pending) (void)hipEventSynchronize(done);
+        pending = false;
+        if (done) (void)hipEventDestroy(done);
+        done = nullptr;
+        PinnedBuffer::release();
+    }
+};
+
 template <typename T>
 int upload(DeviceBuffer& buf, const std::vector<T>& host) {
     int rc = buf.reserve(host.size() * sizeof(T));
@@ -150,7 +204,7 @@ int device_cu_count();
 // 1-2 gave every argument its own hipMalloc + blocking hipMemcpy + hipFree: 0.3 ms for a chain whose arithmetic is
 // microseconds.  A StageCall packs all host inputs of a call into ONE pinned block (one asynchronous upload), hands out
 // device addresses inside one device arena, and brings all outputs back with ONE download and ONE stream synchronisation.
-// The arena (pinned block, device block, stream) is a process-level object created on first use and never freed: no HIP
+// The arena (a PinnedBuffer, a device block, a stream) is a process-level object created on first use and never freed: no HIP
 // call runs from a static or thread-local destructor at exit.  Calls are serialised by its mutex (the reference calls from
 // one GUI thread).  Arguments that already live in device memory pass through untouched; a call with any such argument
 // launches on the null stream, which is ordered behind the (blocking) stream that produced them.

@@ -1869,8 +1869,8 @@ extern "C" void frt_octbank_destroy(frt_octbank* h) {
         if (e) (void)hipEventDestroy(e);
     for (auto& e : h->ev_side)
         if (e) (void)hipEventDestroy(e);
-    if (h->pin_in) (void)hipHostFree(h->pin_in);
-    if (h->pin_out) (void)hipHostFree(h->pin_out);
+    h->pin_in.release();
+    h->pin_out.release();
     frt_ola_destroy(h);
     DeviceBuffer* bufs[] = {&h->coef, &h->order, &h->state, &h->state_snap, &h->xin, &h->ypacked, &h->chunk_end, &h->chunk_init, &h->power, &h->zs_table, &h->zs_table_m, &h->zs_rowmap, &h->eseg,
                             &h->eblock, &h->alpha, &h->decay_n, &h->smooth, &h->weight, &h->eout};
@@ -2333,14 +2333,14 @@ static void snapshot_ptrs(const frt_octbank* h, const void** p) {
 
 static int enqueue_filter(frt_octbank* h, int n, int64_t plen, hipStream_t s) {
     const size_t in_bytes = (size_t)h->n_channels * n * sizeof(double), out_bytes = (size_t)h->n_channels * plen * sizeof(double);
-    FRT_HIP_CHECK(hipMemcpyAsync(h->xin.ptr, h->pin_in, in_bytes, hipMemcpyHostToDevice, s));
+    FRT_HIP_CHECK(hipMemcpyAsync(h->xin.ptr, h->pin_in.ptr, in_bytes, hipMemcpyHostToDevice, s));
     hipStream_t keep = h->stream;
     h->stream = s;
     int rc = h->mode == 1 ? frt_ola_filter(h, h->xin.as<double>(), n, h->ypacked.as<double>(), plen)
                           : run_stages(h, h->xin.ptr, 0, n, n, h->ypacked.as<double>(), plen, nullptr, 0, 0);
     h->stream = keep;
     if (rc) return rc;
-    FRT_HIP_CHECK(hipMemcpyAsync(h->pin_out, h->ypacked.ptr, out_bytes, hipMemcpyDeviceToHost, s));
+    FRT_HIP_CHECK(hipMemcpyAsync(h->pin_out.ptr, h->ypacked.ptr, out_bytes, hipMemcpyDeviceToHost, s));
     return FRT_OK;
 }
 
@@ -2348,26 +2348,18 @@ static int filter_host(frt_octbank* h, const double* x, int n, double* y_packed,
     const size_t in_bytes = (size_t)h->n_channels * n * sizeof(double), out_bytes = (size_t)h->n_channels * plen * sizeof(double);
     int rc;
     if ((rc = h->xin.reserve(in_bytes)) || (rc = h->ypacked.reserve(out_bytes))) return rc;
-    if (in_bytes > h->pin_in_bytes) {
-        if (h->pin_in) (void)hipHostFree(h->pin_in);
-        FRT_HIP_CHECK(hipHostMalloc(&h->pin_in, in_bytes, hipHostMallocDefault));
-        h->pin_in_bytes = in_bytes;
-    }
-    if (out_bytes > h->pin_out_bytes) {
-        if (h->pin_out) (void)hipHostFree(h->pin_out);
-        FRT_HIP_CHECK(hipHostMalloc(&h->pin_out, out_bytes, hipHostMallocDefault));
-        h->pin_out_bytes = out_bytes;
-    }
+    // exactly the need, not twice it: these blocks can be hundreds of MB of page-locked memory
+    if ((rc = h->pin_in.reserve(in_bytes, in_bytes)) || (rc = h->pin_out.reserve(out_bytes, out_bytes))) return rc;
     if (!h->gstream) FRT_HIP_CHECK(hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking));
     FRT_HIP_CHECK(hipStreamSynchronize(h->stream));        // order after earlier work on the caller's stream
-    memcpy(h->pin_in, x, in_bytes);
+    memcpy(h->pin_in.ptr, x, in_bytes);
     const bool no_chunk = option(kOptOlaChunkKernels) == 0;       // tests: the transform path on a call the chunk kernels would serve
     if (h->mode == 1 && n <= 1024 && in_bytes <= kZeroCopyMax && out_bytes <= kZeroCopyMax && !no_chunk) {
         // the production bank's block (Octave_Filters.filter): running convolutions, two launches, samples read and band
         // signals written in place in the page-locked blocks (ola.hip, chunk path) instead of nine transform launches
-        if ((rc = frt_ola_chunk_filter(h, (const double*)h->pin_in, n, (double*)h->pin_out, plen))) return rc;
+        if ((rc = frt_ola_chunk_filter(h, h->pin_in.as<const double>(), n, h->pin_out.as<double>(), plen))) return rc;
         FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-        memcpy(y_packed, h->pin_out, out_bytes);
+        memcpy(y_packed, h->pin_out.ptr, out_bytes);
         return FRT_OK;
     }
 
@@ -2415,7 +2407,7 @@ static int filter_host(frt_octbank* h, const double* x, int n, double* y_packed,
         FRT_HIP_CHECK(hipGraphLaunch(entry.exec, h->gstream));
     }
     FRT_HIP_CHECK(hipStreamSynchronize(h->gstream));
-    memcpy(y_packed, h->pin_out, out_bytes);
+    memcpy(y_packed, h->pin_out.ptr, out_bytes);
     return FRT_OK;
 }
 
@@ -2505,35 +2497,23 @@ extern "C" int frt_octbank_energies(frt_octbank* h, const float* x, int64_t n, i
     if (!dx) {
         if ((rc = h->xin.reserve(xbytes)) || (rc = h->eout.reserve(obytes))) return rc;
         if (pinned) {
-            if (xbytes > h->pin_in_bytes || obytes > h->pin_out_bytes) {
+            if (h->pin_in.grows(xbytes) || h->pin_out.grows(obytes)) {
                 // captured graphs of frt_octbank_filter carry the pinned addresses: they are rebuilt at their next use
                 for (auto& e : h->graphs)
                     if (e.exec) (void)hipGraphExecDestroy(e.exec);
                 h->graphs.clear();
             }
-            if (xbytes > h->pin_in_bytes) {
-                FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-                if (h->pin_in) (void)hipHostFree(h->pin_in);
-                h->pin_in = nullptr;
-                h->pin_in_bytes = 0;
-                FRT_HIP_CHECK(hipHostMalloc(&h->pin_in, 2 * xbytes, hipHostMallocDefault));
-                h->pin_in_bytes = 2 * xbytes;
-            }
-            if (obytes > h->pin_out_bytes) {
-                FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-                if (h->pin_out) (void)hipHostFree(h->pin_out);
-                h->pin_out = nullptr;
-                h->pin_out_bytes = 0;
-                FRT_HIP_CHECK(hipHostMalloc(&h->pin_out, 2 * obytes, hipHostMallocDefault));
-                h->pin_out_bytes = 2 * obytes;
-            }
-            memcpy(h->pin_in, x, xbytes);
+            if (h->pin_in.grows(xbytes)) FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
+            if ((rc = h->pin_in.reserve(xbytes))) return rc;
+            if (h->pin_out.grows(obytes)) FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
+            if ((rc = h->pin_out.reserve(obytes))) return rc;
+            memcpy(h->pin_in.ptr, x, xbytes);
         }
         if (chunk_kernels && pinned) {
-            d_x = h->pin_in;                       // the two launches read the chunk and write the band vector in place
-            d_out = (float*)h->pin_out;
+            d_x = h->pin_in.ptr;                   // the two launches read the chunk and write the band vector in place
+            d_out = h->pin_out.as<float>();
         } else {
-            FRT_HIP_CHECK(hipMemcpyAsync(h->xin.ptr, pinned ? (const void*)h->pin_in : (const void*)x, xbytes, hipMemcpyHostToDevice, h->stream));
+            FRT_HIP_CHECK(hipMemcpyAsync(h->xin.ptr, pinned ? (const void*)h->pin_in.ptr : (const void*)x, xbytes, hipMemcpyHostToDevice, h->stream));
             d_x = h->xin.ptr;
             d_out = h->eout.as<float>();
         }
@@ -2546,7 +2526,7 @@ extern "C" int frt_octbank_energies(frt_octbank* h, const float* x, int64_t n, i
         if (!dx) {
             if (!pinned) FRT_HIP_CHECK(hipMemcpyAsync(energy_out, d_out, obytes, hipMemcpyDeviceToHost, h->stream));
             FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-            if (pinned) memcpy(energy_out, h->pin_out, obytes);
+            if (pinned) memcpy(energy_out, h->pin_out.ptr, obytes);
         }
         return FRT_OK;
     }
@@ -2569,9 +2549,9 @@ extern "C" int frt_octbank_energies(frt_octbank* h, const float* x, int64_t n, i
     }
     FRT_HIP_CHECK(hipGetLastError());
     if (!dx) {
-        FRT_HIP_CHECK(hipMemcpyAsync(pinned ? h->pin_out : (void*)energy_out, d_out, obytes, hipMemcpyDeviceToHost, h->stream));
+        FRT_HIP_CHECK(hipMemcpyAsync(pinned ? h->pin_out.ptr : (void*)energy_out, d_out, obytes, hipMemcpyDeviceToHost, h->stream));
         FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (pinned) memcpy(energy_out, h->pin_out, obytes);
+        if (pinned) memcpy(energy_out, h->pin_out.ptr, obytes);
     }
     return FRT_OK;
 }
@@ -2646,28 +2626,15 @@ extern "C" int frt_decimate_multiple_state(frt_octbank* h, int n_stages, const d
     const size_t in_need = (xbytes + 255) / 256 * 256 + sbytes;
     FRT_REQUIRE(in_need <= kZeroCopyMax && obytes <= kZeroCopyMax, "frt_decimate_multiple_state: %d samples x %d channels exceed the in-place call", n, C);
     int rc;
-    if (in_need > h->pin_in_bytes || obytes > h->pin_out_bytes) {
+    if (h->pin_in.grows(in_need) || h->pin_out.grows(obytes)) {
         FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
         for (auto& e : h->graphs)                              // captured graphs carry the pinned addresses
             if (e.exec) (void)hipGraphExecDestroy(e.exec);
         h->graphs.clear();
-        if (in_need > h->pin_in_bytes) {
-            if (h->pin_in) (void)hipHostFree(h->pin_in);
-            h->pin_in = nullptr;
-            h->pin_in_bytes = 0;
-            FRT_HIP_CHECK(hipHostMalloc(&h->pin_in, 2 * in_need, hipHostMallocDefault));
-            h->pin_in_bytes = 2 * in_need;
-        }
-        if (obytes > h->pin_out_bytes) {
-            if (h->pin_out) (void)hipHostFree(h->pin_out);
-            h->pin_out = nullptr;
-            h->pin_out_bytes = 0;
-            FRT_HIP_CHECK(hipHostMalloc(&h->pin_out, 2 * obytes, hipHostMallocDefault));
-            h->pin_out_bytes = 2 * obytes;
-        }
     }
-    double* px = (double*)h->pin_in;
-    double* ps = (double*)((char*)h->pin_in + (xbytes + 255) / 256 * 256);      // [stage][channel][kStates]: the kernel's layout
+    if ((rc = h->pin_in.reserve(in_need)) || (rc = h->pin_out.reserve(obytes))) return rc;
+    double* px = h->pin_in.as<double>();
+    double* ps = (double*)(h->pin_in.as<char>() + (xbytes + 255) / 256 * 256);      // [stage][channel][kStates]: the kernel's layout
     memcpy(px, x, xbytes);
     for (int j = 0; j < n_stages; ++j)
         for (int c = 0; c < C; ++c)
@@ -2689,12 +2656,12 @@ extern "C" int frt_decimate_multiple_state(frt_octbank* h, int n_stages, const d
         a.nchunks = 1;
         a.pass = 0;
         a.band_index[0] = -1;
-        a.xnext = j + 1 == n_stages ? (double*)h->pin_out : h->xbuf[j + 1].as<double>();
+        a.xnext = j + 1 == n_stages ? h->pin_out.as<double>() : h->xbuf[j + 1].as<double>();
         a.xnext_stride = len[j + 1];
         if ((rc = launch_iir_stage(a, h->h_order.data(), C, h->stream))) return rc;
     }
     FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-    memcpy(out, h->pin_out, obytes);
+    memcpy(out, h->pin_out.ptr, obytes);
     if (zf)
         for (int j = 0; j < n_stages; ++j)
             for (int c = 0; c < C; ++c)
@@ -2856,11 +2823,8 @@ struct frt_delay {
     DeviceBuffer ring;                      // [2][2 ring_len]
     long long ring_len = 0, offset = 0;     // offset: decimated samples pushed so far
     static constexpr int kSlots = 4;        // pinned chunks in flight
-    char* pin[kSlots] = {};
-    size_t pin_bytes[kSlots] = {};
-    hipEvent_t done[kSlots] = {};
-    bool pending[kSlots] = {};
-    int slot = 0;
+    PinnedSlot slot[kSlots];
+    int next_slot = 0;
     DeviceBuffer stats, xin;
 };
 
@@ -2871,10 +2835,7 @@ extern "C" void frt_delay_destroy(frt_delay* h) {
     h->ring.release();
     h->stats.release();
     h->xin.release();
-    for (int s = 0; s < frt_delay::kSlots; ++s) {
-        if (h->pin[s]) (void)hipHostFree(h->pin[s]);
-        if (h->done[s]) (void)hipEventDestroy(h->done[s]);
-    }
+    for (PinnedSlot& s : h->slot) s.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -2890,8 +2851,6 @@ extern "C" int frt_delay_create(frt_delay** out, const double* bdec, const doubl
     int rc = frt_octbank_create(&h->dec, 0, 2, 0, nullptr, nullptr, bdec, adec, nullptr, nullptr);
     if (!rc && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) rc = FRT_ERR_HIP;
     if (!rc) rc = frt_octbank_set_stream(h->dec, h->stream);
-    for (int s = 0; !rc && s < frt_delay::kSlots; ++s)
-        if (hipEventCreateWithFlags(&h->done[s], hipEventDisableTiming) != hipSuccess) rc = FRT_ERR_HIP;
     if (!rc) rc = h->ring.reserve((size_t)2 * 2 * ring_length * sizeof(double));
     if (!rc) rc = h->stats.reserve(2 * sizeof(double));
     if (!rc && hipMemsetAsync(h->ring.ptr, 0, h->ring.bytes, h->stream) != hipSuccess) rc = FRT_ERR_HIP;
@@ -2940,25 +2899,14 @@ extern "C" int frt_delay_push(frt_delay* h, const double* x, int n, int64_t* off
     int rc;
     if (m > h->ring_len && (rc = frt_delay_reserve(h, m))) return rc;
     // the chunk travels through a pinned slot (an asynchronous copy needs page-locked memory to be asynchronous)
-    const int s = h->slot;
-    h->slot = (s + 1) % frt_delay::kSlots;
-    if (h->pending[s]) {
-        FRT_HIP_CHECK(hipEventSynchronize(h->done[s]));
-        h->pending[s] = false;
-    }
+    PinnedSlot& s = h->slot[h->next_slot];
+    h->next_slot = (h->next_slot + 1) % frt_delay::kSlots;
     const size_t xbytes = (size_t)2 * n * sizeof(double);
-    if (xbytes > h->pin_bytes[s]) {
-        if (h->pin[s]) (void)hipHostFree(h->pin[s]);
-        h->pin[s] = nullptr;
-        h->pin_bytes[s] = 0;
-        FRT_HIP_CHECK(hipHostMalloc((void**)&h->pin[s], 2 * xbytes, hipHostMallocDefault));
-        h->pin_bytes[s] = 2 * xbytes;
-    }
-    memcpy(h->pin[s], x, xbytes);
+    if ((rc = s.wait()) || (rc = s.reserve(xbytes))) return rc;
+    memcpy(s.ptr, x, xbytes);
     if ((rc = h->xin.reserve(xbytes))) return rc;
-    FRT_HIP_CHECK(hipMemcpyAsync(h->xin.ptr, h->pin[s], xbytes, hipMemcpyHostToDevice, h->stream));
-    FRT_HIP_CHECK(hipEventRecord(h->done[s], h->stream));
-    h->pending[s] = true;
+    FRT_HIP_CHECK(hipMemcpyAsync(h->xin.ptr, s.ptr, xbytes, hipMemcpyHostToDevice, h->stream));
+    if ((rc = s.mark(h->stream))) return rc;
     frt_octbank* d = h->dec;
     for (int j = 1; j <= h->n_stages; ++j)
         if ((rc = d->xbuf[j].reserve((size_t)2 * len[j] * sizeof(double)))) return rc;
@@ -3009,7 +2957,7 @@ extern "C" int frt_delay_window_std(frt_delay* h, const double* d0, const double
     FRT_HIP_CHECK(hipGetLastError());
     FRT_HIP_CHECK(hipMemcpyAsync(std_out, h->stats.ptr, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-    for (int s = 0; s < frt_delay::kSlots; ++s) h->pending[s] = false;
+    for (PinnedSlot& s : h->slot) s.forget();
     return FRT_OK;
 }
 

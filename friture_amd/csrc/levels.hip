@@ -348,25 +348,10 @@ struct frt_levels {
     DeviceBuffer kern, state[2], ring, xin, us, ud, mt, outs, hist;
     int cur = 0;
     long long r = 0, ring_total = 0;
-    double* pin = nullptr;
-    size_t pin_bytes = 0;
+    PinnedBuffer pin;
 };
 
 namespace {
-
-int pin_reserve(frt_levels* h, size_t bytes) {
-    if (bytes <= h->pin_bytes) return FRT_OK;
-    if (h->pin) {
-        FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-        (void)hipHostFree(h->pin);
-        h->pin = nullptr;
-        h->pin_bytes = 0;
-    }
-    bytes = std::max(bytes, (size_t)1 << 16);
-    FRT_HIP_CHECK(hipHostMalloc((void**)&h->pin, bytes, hipHostMallocDefault));
-    h->pin_bytes = bytes;
-    return FRT_OK;
-}
 
 // the initial state of one channel: levels.py:66-69,76 (old_rms = old_max = 1e-30), ballistic_peak.py:27-29
 void initial_meta(double* m, double rate) {
@@ -533,7 +518,7 @@ extern "C" void frt_levels_destroy(frt_levels* h) {
     if (!h) return;
     (void)hipStreamSynchronize(h->stream);
     for (DeviceBuffer* b : {&h->kern, &h->state[0], &h->state[1], &h->ring, &h->xin, &h->us, &h->ud, &h->mt, &h->outs, &h->hist}) b->release();
-    if (h->pin) (void)hipHostFree(h->pin);
+    h->pin.release();
     delete h;
     free_retired_allocations(true);
 }
@@ -647,19 +632,21 @@ extern "C" int frt_levels_push(frt_levels* h, const double* x_host, int nch, int
     const size_t lbytes = long_out ? (size_t)nch * nb * 2 * sizeof(double) : 0;
     const size_t xround = (xbytes + 255) / 256 * 256;
     int rc;
-    if ((rc = pin_reserve(h, xround + mbytes + lbytes))) return rc;
-    if ((rc = h->xin.reserve(std::max<size_t>(xround + mbytes + lbytes, 64)))) return rc;
+    const size_t pin_need = xround + mbytes + lbytes;
+    if (h->pin.ptr && h->pin.grows(pin_need)) FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
+    if ((rc = h->pin.reserve(pin_need, std::max(pin_need, (size_t)1 << 16)))) return rc;
+    if ((rc = h->xin.reserve(std::max<size_t>(pin_need, 64)))) return rc;
     // one upload, the launches, one download
     if (xbytes) {
         FRT_HIP_CHECK(hipStreamSynchronize(h->stream));      // the pinned block may still be the source of the previous upload
-        memcpy(h->pin, x_host, xbytes);
-        FRT_HIP_CHECK(hipMemcpyAsync(h->xin.ptr, h->pin, xbytes, hipMemcpyHostToDevice, h->stream));
+        memcpy(h->pin.ptr, x_host, xbytes);
+        FRT_HIP_CHECK(hipMemcpyAsync(h->xin.ptr, h->pin.ptr, xbytes, hipMemcpyHostToDevice, h->stream));
     }
     double* dm = meters_out ? reinterpret_cast<double*>(h->xin.as<char>() + xround) : nullptr;
     double* dl = long_out ? reinterpret_cast<double*>(h->xin.as<char>() + xround + mbytes) : nullptr;
     if ((rc = run_device(h, h->xin.ptr, 1, n, n, nch, n > 0 ? n : 1, 1, dm, dl, false, nullptr))) return rc;
     if (mbytes + lbytes) {
-        char* back = reinterpret_cast<char*>(h->pin) + xround;
+        char* back = h->pin.as<char>() + xround;
         FRT_HIP_CHECK(hipMemcpyAsync(back, h->xin.as<char>() + xround, mbytes + lbytes, hipMemcpyDeviceToHost, h->stream));
         FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
         if (mbytes) memcpy(meters_out, back, mbytes);

@@ -81,9 +81,9 @@ namespace {
 struct StageArena {
     std::mutex mu;
     hipStream_t stream = nullptr;
-    char* pin = nullptr;
+    PinnedBuffer pinned;
     char* dev = nullptr;
-    size_t pin_bytes = 0, dev_bytes = 0;
+    size_t dev_bytes = 0;
 };
 StageArena& arena() {
     static StageArena* a = new StageArena();          // never destroyed: see common.h
@@ -128,14 +128,9 @@ int StageCall::begin() {
     StageArena& a = arena();
     if (!a.stream) FRT_HIP_CHECK(hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking));
     const size_t host_need = in_bytes_ + out_bytes_, dev_need = in_bytes_ + out_bytes_ + scratch_bytes_;
-    if (host_need > a.pin_bytes) {
-        FRT_HIP_CHECK(hipStreamSynchronize(a.stream));
-        if (a.pin) (void)hipHostFree(a.pin);
-        a.pin = nullptr;
-        a.pin_bytes = 0;
-        FRT_HIP_CHECK(hipHostMalloc((void**)&a.pin, 2 * host_need + 4096, hipHostMallocDefault));
-        a.pin_bytes = 2 * host_need + 4096;
-    }
+    if (a.pinned.grows(host_need)) FRT_HIP_CHECK(hipStreamSynchronize(a.stream));
+    if (int rc = a.pinned.reserve(host_need, 2 * host_need + 4096)) return rc;
+    char* const pin = a.pinned.as<char>();
     if (dev_need > a.dev_bytes) {
         FRT_HIP_CHECK(hipStreamSynchronize(a.stream));
         if (a.dev) (void)hipFree(a.dev);
@@ -152,23 +147,24 @@ int StageCall::begin() {
     for (Arg& g : arg_) {
         if (!g.staged) continue;
         const size_t base = g.kind == 0 ? 0 : g.kind == 1 ? in_bytes_ : in_bytes_ + out_bytes_;
-        g.dev = (zero_copy_ && g.kind != 2) ? a.pin + base + g.off : a.dev + base + g.off;
-        if (g.kind == 0 && g.bytes) memcpy(a.pin + g.off, g.src, g.bytes);
+        g.dev = (zero_copy_ && g.kind != 2) ? pin + base + g.off : a.dev + base + g.off;
+        if (g.kind == 0 && g.bytes) memcpy(pin + g.off, g.src, g.bytes);
     }
     // device-resident arguments were produced on a stream this call does not know: the null stream waits for the blocking ones
     launch_stream_ = any_device_ ? nullptr : a.stream;
-    if (in_bytes_ && !zero_copy_) FRT_HIP_CHECK(hipMemcpyAsync(a.dev, a.pin, in_bytes_, hipMemcpyHostToDevice, launch_stream_));
+    if (in_bytes_ && !zero_copy_) FRT_HIP_CHECK(hipMemcpyAsync(a.dev, pin, in_bytes_, hipMemcpyHostToDevice, launch_stream_));
     return FRT_OK;
 }
 
 int StageCall::finish() {
     StageArena& a = arena();
+    char* const pin = a.pinned.as<char>();
     FRT_HIP_CHECK(hipGetLastError());
     if (out_bytes_ && !zero_copy_)
-        FRT_HIP_CHECK(hipMemcpyAsync(a.pin + in_bytes_, a.dev + in_bytes_, out_bytes_, hipMemcpyDeviceToHost, launch_stream_));
+        FRT_HIP_CHECK(hipMemcpyAsync(pin + in_bytes_, a.dev + in_bytes_, out_bytes_, hipMemcpyDeviceToHost, launch_stream_));
     FRT_HIP_CHECK(hipStreamSynchronize(launch_stream_));
     for (const Arg& g : arg_)
-        if (g.staged && g.kind == 1 && g.bytes) memcpy(g.dst, a.pin + in_bytes_ + g.off, g.bytes);
+        if (g.staged && g.kind == 1 && g.bytes) memcpy(g.dst, pin + in_bytes_ + g.off, g.bytes);
     return FRT_OK;
 }
 

@@ -77,9 +77,7 @@ struct frt_octbank {
     };
     std::vector<StreamGraph> graphs;
     hipStream_t gstream = nullptr;
-    void* pin_in = nullptr;
-    void* pin_out = nullptr;
-    size_t pin_in_bytes = 0, pin_out_bytes = 0;
+    frt::PinnedBuffer pin_in, pin_out;
     int warmed_n = -1;
     bool use_graph = true;
     size_t stage_state_elems() const { return (size_t)n_channels * nfilt * frt::kStates; }

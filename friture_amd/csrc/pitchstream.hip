@@ -166,25 +166,6 @@ __global__ void __launch_bounds__(kThreads) live_finish_kernel(const FinishArgs 
     }
 }
 
-struct Pinned {
-    void* ptr = nullptr;
-    size_t bytes = 0;
-    int reserve(size_t n) {             // only between pushes: every push ends in a synchronisation
-        if (n <= bytes) return FRT_OK;
-        if (ptr) (void)hipHostFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-        FRT_HIP_CHECK(hipHostMalloc(&ptr, 2 * n, hipHostMallocDefault));
-        bytes = 2 * n;
-        return FRT_OK;
-    }
-    void release() {
-        if (ptr) (void)hipHostFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-    }
-};
-
 }  // namespace
 }  // namespace frt
 
@@ -196,7 +177,7 @@ struct frt_pitch_live {
     long long M = 0;
     double trans_min = 0, trans_span = 0;
     DeviceBuffer prev, history, in, energy, raw, out;       // history: [2][M], `current` holds the state
-    Pinned pin_in, pin_out;
+    PinnedBuffer pin_in, pin_out;       // reserved only between pushes: every push ends in a synchronisation
 };
 
 extern "C" void frt_pitch_live_destroy(frt_pitch_live* h) {

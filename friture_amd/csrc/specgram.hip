@@ -139,12 +139,8 @@ struct frt_specgram {
     bool has_map = false, has_lut = false;
     // Online_Linear_2D_resampler's scalars (online_linear_2D_resampler.py:21-43)
     double interp_L = 1.0, decim_M = 1.0, ratio = 1.0, orig_index = 0.0, resampled_index = 0.0;
-    void* pin = nullptr;
-    size_t pin_bytes = 0;
-    void* pin_in = nullptr;
-    size_t pin_in_bytes = 0;
-    hipEvent_t in_done = nullptr;                // the last chunk has left the staging buffers (pin_in, chunk)
-    bool in_pending = false;
+    PinnedBuffer pin;                            // pixels for a host caller
+    PinnedSlot pin_in;                           // its event: the last chunk has left the staging buffers (pin_in, chunk)
     std::vector<int> h_src;
     std::vector<double> h_a;
 };
@@ -155,9 +151,8 @@ extern "C" void frt_specgram_destroy(frt_specgram* h) {
     DeviceBuffer* bufs[] = {&h->ring, &h->chunk, &h->norm, &h->jidx, &h->dx, &h->den, &h->old_a, &h->old_b, &h->src, &h->a, &h->lut,
                             &h->pixels};
     for (auto* b : bufs) b->release();
-    if (h->pin) (void)hipHostFree(h->pin);
-    if (h->pin_in) (void)hipHostFree(h->pin_in);
-    if (h->in_done) (void)hipEventDestroy(h->in_done);
+    h->pin.release();
+    h->pin_in.release();
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -183,7 +178,6 @@ extern "C" int frt_specgram_create(frt_specgram** out, int fft_size, double over
         h->own_stream = true;
         rc = frt_stft_set_stream(h->stft, h->stream);
     }
-    if (!rc && hipEventCreateWithFlags(&h->in_done, hipEventDisableTiming) != hipSuccess) rc = FRT_ERR_HIP;
     if (!rc) rc = h->ring.reserve(2 * (size_t)ring_length * sizeof(double));
     if (!rc && hipMemsetAsync(h->ring.ptr, 0, h->ring.bytes, h->stream) != hipSuccess) rc = FRT_ERR_HIP;
     if (rc) {
@@ -322,34 +316,23 @@ extern "C" int frt_specgram_push(frt_specgram* h, const double* chunk, int n, ui
     if (n > 0) {
         // the staging buffers are reused from push to push: the previous chunk must have left them (a push that completes
         // no frame returns without waiting for its copy)
-        if (h->in_pending) {
-            FRT_HIP_CHECK(hipEventSynchronize(h->in_done));
-            h->in_pending = false;
-        }
+        if ((rc = h->pin_in.wait())) return rc;
         if ((rc = h->chunk.reserve((size_t)n * sizeof(double)))) return rc;
         // through pinned memory: a copy from pageable memory is staged by the runtime and blocks the calling thread
-        if ((size_t)n * sizeof(double) > h->pin_in_bytes) {
-            if (h->pin_in) (void)hipHostFree(h->pin_in);
-            h->pin_in = nullptr;
-            h->pin_in_bytes = 0;
-            FRT_HIP_CHECK(hipHostMalloc(&h->pin_in, (size_t)n * sizeof(double) * 2, hipHostMallocDefault));
-            h->pin_in_bytes = (size_t)n * sizeof(double) * 2;
-        }
-        memcpy(h->pin_in, chunk, (size_t)n * sizeof(double));
+        if ((rc = h->pin_in.reserve((size_t)n * sizeof(double)))) return rc;
+        memcpy(h->pin_in.ptr, chunk, (size_t)n * sizeof(double));
         // a widget-sized chunk is read by the ring write where it lies (page-locked memory is device accessible): one launch
         // instead of a copy and a launch; long chunks go up by the copy engine first
-        const double* src = (const double*)h->pin_in;
+        const double* src = h->pin_in.as<double>();
         if ((size_t)n * sizeof(double) > kZeroCopyMax) {
-            FRT_HIP_CHECK(hipMemcpyAsync(h->chunk.ptr, h->pin_in, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            FRT_HIP_CHECK(hipMemcpyAsync(h->chunk.ptr, h->pin_in.ptr, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
             src = h->chunk.as<double>();
         }
         hipLaunchKernelGGL(ring_write_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, src, n, h->ring.as<double>(), h->ring_len,
                            h->offset);
         FRT_HIP_CHECK(hipGetLastError());
-        if (realizable <= 0) {                     // a push that completes frames waits for the stream at its end anyway
-            FRT_HIP_CHECK(hipEventRecord(h->in_done, h->stream));
-            h->in_pending = true;
-        }
+        // a push that completes frames waits for the stream at its end anyway
+        if (realizable <= 0 && (rc = h->pin_in.mark(h->stream))) return rc;
     }
     h->offset = new_offset;
     h->old_index = new_old_index;
@@ -388,18 +371,14 @@ extern "C" int frt_specgram_push(frt_specgram* h, const double* chunk, int n, ui
     const size_t pix_bytes = (size_t)n_out * h->height * 4;
     const bool host_out = n_out > 0 && pixels_out && !is_device_pointer(pixels_out);
     const bool direct_out = host_out && pix_bytes <= kZeroCopyMax;
-    if (host_out && pix_bytes > h->pin_bytes) {
-        FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (h->pin) (void)hipHostFree(h->pin);
-        h->pin = nullptr;
-        h->pin_bytes = 0;
-        FRT_HIP_CHECK(hipHostMalloc(&h->pin, pix_bytes * 2, hipHostMallocDefault));
-        h->pin_bytes = pix_bytes * 2;
+    if (host_out) {
+        if (h->pin.grows(pix_bytes)) FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
+        if ((rc = h->pin.reserve(pix_bytes))) return rc;
     }
     hipLaunchKernelGGL(screen_columns_kernel, dim3((cols_alloc + 63) / 64, h->height), dim3(64), 0, h->stream, h->norm.as<double>(), h->nb,
                        realizable, h->jidx.as<int>(), h->dx.as<double>(), h->den.as<double>(), h->height, old_in.as<double>(),
                        old_out.as<double>(), inline_cols ? nullptr : h->src.as<int>(), inline_cols ? nullptr : h->a.as<double>(), inl, n_out,
-                       h->lut.as<uint32_t>(), direct_out ? (uint32_t*)h->pin : h->pixels.as<uint32_t>(), n_out > 0 ? n_out : 1, 1);
+                       h->lut.as<uint32_t>(), direct_out ? h->pin.as<uint32_t>() : h->pixels.as<uint32_t>(), n_out > 0 ? n_out : 1, 1);
     FRT_HIP_CHECK(hipGetLastError());
     h->old_is_a = !h->old_is_a;
     if (n_out > 0 && pixels_out) {
@@ -407,14 +386,14 @@ extern "C" int frt_specgram_push(frt_specgram* h, const double* chunk, int n, ui
             FRT_HIP_CHECK(hipMemcpy2DAsync(pixels_out, (size_t)max_cols * 4, h->pixels.ptr, (size_t)n_out * 4, (size_t)n_out * 4, h->height,
                                            hipMemcpyDeviceToDevice, h->stream));
         } else {
-            if (!direct_out) FRT_HIP_CHECK(hipMemcpyAsync(h->pin, h->pixels.ptr, pix_bytes, hipMemcpyDeviceToHost, h->stream));
+            if (!direct_out) FRT_HIP_CHECK(hipMemcpyAsync(h->pin.ptr, h->pixels.ptr, pix_bytes, hipMemcpyDeviceToHost, h->stream));
             FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
             for (int r = 0; r < h->height; ++r)
-                memcpy(pixels_out + (size_t)r * max_cols, (const uint32_t*)h->pin + (size_t)r * n_out, (size_t)n_out * 4);
+                memcpy(pixels_out + (size_t)r * max_cols, h->pin.as<uint32_t>() + (size_t)r * n_out, (size_t)n_out * 4);
         }
     }
     FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-    h->in_pending = false;
+    h->pin_in.forget();
     *n_cols_out = n_out;
     return FRT_OK;
 }

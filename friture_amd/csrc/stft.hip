@@ -232,10 +232,8 @@ struct frt_stft {
     bool has_weight = false, has_lut = false;
     double spec_min = -140.0, spec_max = 0.0;
     DeviceBuffer stage_in, stage_out;
-    char* pin = nullptr;          // pinned staging of the host-buffer path: [input][output]
-    size_t pin_bytes = 0;
-    hipEvent_t pin_done = nullptr;     // host samples -> device spectra returns without waiting: guards the pinned block
-    bool pin_pending = false;
+    PinnedSlot pin;               // pinned staging of the host-buffer path: [input][output]; host samples -> device spectra
+                                  // returns without waiting: the slot's event guards the block
 };
 
 template <typename T>
@@ -309,9 +307,7 @@ extern "C" void frt_stft_destroy(frt_stft* h) {
     h->lut.release();
     h->stage_in.release();
     h->stage_out.release();
-    if (h->pin_pending) (void)hipEventSynchronize(h->pin_done);
-    if (h->pin_done) (void)hipEventDestroy(h->pin_done);
-    if (h->pin) (void)hipHostFree(h->pin);
+    h->pin.release();
     delete h;
 }
 
@@ -547,36 +543,24 @@ static int stft_run(frt_stft* h, int kind, const void* x, int64_t T, int64_t x_s
     const size_t in_esz = h->precision == 32 ? 4 : 8;
     const size_t out_esz = (kind == FRT_STFT_IMAGE) ? 4 : in_esz;
     if (dx) return stft_launch(h, kind, x, x_stride, out, nyq, F, h->stream);
-    if (h->pin_pending) {                        // an earlier host -> device call may still be reading the pinned block
-        FRT_HIP_CHECK(hipEventSynchronize(h->pin_done));
-        h->pin_pending = false;
-    }
+    int rc;
+    if ((rc = h->pin.wait())) return rc;         // an earlier host -> device call may still be reading the pinned block
     if (dout) {
         // host samples, spectra that stay on the device (a widget's ring on the host, its read-out chain on the device):
         // the samples go through the pinned block — read in place by the kernel when small — and the call returns without
         // waiting; consumers order themselves on the handle's stream
         const size_t in_bytes = (size_t)h->n_channels * x_stride * in_esz;
-        int rc;
-        if (in_bytes > h->pin_bytes) {
-            FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-            if (h->pin) (void)hipHostFree(h->pin);
-            h->pin = nullptr;
-            h->pin_bytes = 0;
-            FRT_HIP_CHECK(hipHostMalloc((void**)&h->pin, 2 * in_bytes, hipHostMallocDefault));
-            h->pin_bytes = 2 * in_bytes;
-        }
-        memcpy(h->pin, x, in_bytes);
-        const void* src = h->pin;
+        if (h->pin.grows(in_bytes)) FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
+        if ((rc = h->pin.reserve(in_bytes))) return rc;
+        memcpy(h->pin.ptr, x, in_bytes);
+        const void* src = h->pin.ptr;
         if (in_bytes > kZeroCopyMax) {
             if ((rc = h->stage_in.reserve(in_bytes))) return rc;
-            FRT_HIP_CHECK(hipMemcpyAsync(h->stage_in.ptr, h->pin, in_bytes, hipMemcpyHostToDevice, h->stream));
+            FRT_HIP_CHECK(hipMemcpyAsync(h->stage_in.ptr, h->pin.ptr, in_bytes, hipMemcpyHostToDevice, h->stream));
             src = h->stage_in.ptr;
         }
         if ((rc = stft_launch(h, kind, src, x_stride, out, nyq, F, h->stream))) return rc;
-        if (!h->pin_done) FRT_HIP_CHECK(hipEventCreateWithFlags(&h->pin_done, hipEventDisableTiming));
-        FRT_HIP_CHECK(hipEventRecord(h->pin_done, h->stream));
-        h->pin_pending = true;
-        return FRT_OK;
+        return h->pin.mark(h->stream);
     }
 
     // host buffers: stage through device memory, return when the result is back.  Small calls (the widgets' one frame at a
@@ -585,41 +569,37 @@ static int stft_run(frt_stft* h, int kind, const void* x, int64_t T, int64_t x_s
     const size_t in_bytes = (size_t)h->n_channels * x_stride * in_esz;
     const size_t row_bytes = (size_t)h->n_channels * F * nb * out_esz;                       // split: the Nyquist plane follows the rows
     const size_t out_bytes = row_bytes + (split ? (size_t)h->n_channels * F * out_esz : 0);
-    int rc;
     if ((rc = h->stage_in.reserve(in_bytes))) return rc;
     if ((rc = h->stage_out.reserve(out_bytes))) return rc;
     const size_t in_pad = (in_bytes + 255) / 256 * 256;
     const bool pinned = in_pad + out_bytes <= (size_t)1 << 22;
-    if (pinned && in_pad + out_bytes > h->pin_bytes) {
-        FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (h->pin) (void)hipHostFree(h->pin);
-        h->pin = nullptr;
-        h->pin_bytes = 0;
-        FRT_HIP_CHECK(hipHostMalloc((void**)&h->pin, 2 * (in_pad + out_bytes), hipHostMallocDefault));
-        h->pin_bytes = 2 * (in_pad + out_bytes);
+    if (pinned) {
+        if (h->pin.grows(in_pad + out_bytes)) FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
+        if ((rc = h->pin.reserve(in_pad + out_bytes))) return rc;
+        memcpy(h->pin.ptr, x, in_bytes);
     }
-    if (pinned) memcpy(h->pin, x, in_bytes);
+    char* const pin = h->pin.as<char>();
     if (pinned && in_pad + out_bytes <= kZeroCopyMax) {
         // one frame or a few (audioproc.analyzelive): the kernel reads the pinned block and writes the spectrum into it — no
         // copy engine on either side, one launch and one synchronisation per call
-        if ((rc = stft_launch(h, kind, h->pin, x_stride, h->pin + in_pad, split ? h->pin + in_pad + row_bytes : nullptr, F, h->stream))) return rc;
+        if ((rc = stft_launch(h, kind, pin, x_stride, pin + in_pad, split ? pin + in_pad + row_bytes : nullptr, F, h->stream))) return rc;
         FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-        memcpy(out, h->pin + in_pad, row_bytes);
-        if (split) memcpy(nyq, h->pin + in_pad + row_bytes, out_bytes - row_bytes);
+        memcpy(out, pin + in_pad, row_bytes);
+        if (split) memcpy(nyq, pin + in_pad + row_bytes, out_bytes - row_bytes);
         return FRT_OK;
     }
-    FRT_HIP_CHECK(hipMemcpyAsync(h->stage_in.ptr, pinned ? (const void*)h->pin : x, in_bytes, hipMemcpyHostToDevice, h->stream));
+    FRT_HIP_CHECK(hipMemcpyAsync(h->stage_in.ptr, pinned ? (const void*)pin : x, in_bytes, hipMemcpyHostToDevice, h->stream));
     if ((rc = stft_launch(h, kind, h->stage_in.ptr, x_stride, h->stage_out.ptr, split ? (char*)h->stage_out.ptr + row_bytes : nullptr, F, h->stream))) return rc;
     if (pinned) {
-        FRT_HIP_CHECK(hipMemcpyAsync(h->pin + in_pad, h->stage_out.ptr, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        FRT_HIP_CHECK(hipMemcpyAsync(pin + in_pad, h->stage_out.ptr, out_bytes, hipMemcpyDeviceToHost, h->stream));
     } else {
         FRT_HIP_CHECK(hipMemcpyAsync(out, h->stage_out.ptr, row_bytes, hipMemcpyDeviceToHost, h->stream));
         if (split) FRT_HIP_CHECK(hipMemcpyAsync(nyq, (char*)h->stage_out.ptr + row_bytes, out_bytes - row_bytes, hipMemcpyDeviceToHost, h->stream));
     }
     FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
     if (pinned) {
-        memcpy(out, h->pin + in_pad, row_bytes);
-        if (split) memcpy(nyq, h->pin + in_pad + row_bytes, out_bytes - row_bytes);
+        memcpy(out, pin + in_pad, row_bytes);
+        if (split) memcpy(nyq, pin + in_pad + row_bytes, out_bytes - row_bytes);
     }
     return FRT_OK;
 }
