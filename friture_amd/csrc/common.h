@@ -121,8 +121,9 @@ struct DeviceBuffer {
 
 // A grow-only page-locked host block: the staging of every handle that accepts host arrays.  Two rules for its users: a site
 // allocates the byte count it chose (`alloc`: most double their need, some must not), and whatever has to precede a
-// reallocation — synchronising the stream that may still use the block, dropping captured graphs that carry its address —
-// is done by the site, inside `if (buf.grows(need)) { ... }`, before reserve().  A failed allocation leaves an empty buffer.
+// reallocation — synchronising the stream that may still use the block — is done by the site, inside
+// `if (buf.grows(need)) { ... }`, before reserve().  (Captured graphs that carry the address look after themselves: iir.hip,
+// find_graph.)  A failed allocation leaves an empty buffer.
 struct PinnedBuffer {
     void* ptr = nullptr;
     size_t bytes = 0;

@@ -1,5 +1,5 @@
-// octbank.h — the octave-bank handle shared by the exact IIR path (iir.hip) and the FFT
-// overlap-add path (ola.hip).
+// octbank.h — the octave-bank handle shared by the exact IIR path (iir.hip), the FFT
+// overlap-add path (ola.hip) and the delay estimator's ring object (delay.hip: a decimator-only handle).
 #pragma once
 #include "common.h"
 #include "fft_mixed.h"
@@ -31,7 +31,7 @@ struct frt_ola_state {
     frt::DeviceBuffer btw, btwl, bH, bHw, ewt;
     frt::DeviceBuffer multi_tab[2];     // argument tables of ola_pair_multi_kernel, one per parity of the tails' swap
     std::vector<char> multi_host[2];    // what each holds
-    void* multi_pin[2] = {nullptr, nullptr};   // page-locked staging of the tables' uploads (an async copy keeps its source pointer)
+    frt::PinnedBuffer multi_pin[2];     // page-locked staging of the tables' uploads (an async copy keeps its source pointer)
     int multi_parity = 0;
     std::vector<long long> ewt_off;     // per band: offset of its smoothing weights in ewt
     int ewt_block = 0;
@@ -73,7 +73,7 @@ struct frt_octbank {
     struct StreamGraph {
         int n = 0;
         hipGraphExec_t exec = nullptr;
-        const void* ptrs[2 + frt::kNOctave] = {};     // device buffers baked into the graph
+        const void* ptrs[4 + frt::kNOctave] = {};     // blocks baked into the graph: device buffers and the two pinned ones
     };
     std::vector<StreamGraph> graphs;
     hipStream_t gstream = nullptr;
@@ -83,6 +83,11 @@ struct frt_octbank {
     size_t stage_state_elems() const { return (size_t)n_channels * nfilt * frt::kStates; }
 };
 
+
+// implemented in iir.hip: the first n_stages decimator stages of a bands_per_octave == 0 handle, sequential mode, every
+// channel, enqueued on `stream`.  Stage j reads x [C][n] (j == 0) or xbuf[j], carries state + j * C * kStates and
+// writes xbuf[j + 1] — the last stage writes last_out instead when one is given.  It reserves the xbuf blocks it writes.
+int frt_decimator_chain(frt_octbank* h, int n_stages, const void* x, int n, double* state, double* last_out, hipStream_t stream);
 
 // implemented in ola.hip
 int frt_ola_create(frt_octbank* h, const double* boct_fir, const double* bdec_fir);

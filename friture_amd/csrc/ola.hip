@@ -206,7 +206,7 @@ void frt_ola_destroy(frt_octbank* h) {
     h->ola->xs.release();
     for (int p = 0; p < 2; ++p) {
         h->ola->multi_tab[p].release();
-        if (h->ola->multi_pin[p]) (void)hipHostFree(h->ola->multi_pin[p]);
+        h->ola->multi_pin[p].release();
     }
     delete h->ola;
     h->ola = nullptr;
@@ -824,11 +824,12 @@ int frt_ola_filter_batch(frt_octbank* h, const void* d_x, int x_f32, int64_t n, 
         std::vector<char>& held = o->multi_host[parity];
         if (held.size() != bytes || memcmp(held.data(), deferred.data(), bytes) != 0) {
             if ((rc = o->multi_tab[parity].reserve(kNOctave * sizeof(OlaBatchArgs)))) return rc;
-            if (!o->multi_pin[parity]) FRT_HIP_CHECK(hipHostMalloc(&o->multi_pin[parity], kNOctave * sizeof(OlaBatchArgs), hipHostMallocDefault));
-            else FRT_HIP_CHECK(hipStreamSynchronize(h->stream));      // (an earlier upload from this block may still be queued)
-            held.assign((const char*)deferred.data(), (const char*)deferred.data() + bytes);
-            memcpy(o->multi_pin[parity], held.data(), bytes);
-            FRT_HIP_CHECK(hipMemcpyAsync(o->multi_tab[parity].ptr, o->multi_pin[parity], bytes, hipMemcpyHostToDevice, h->stream));
+            PinnedBuffer& pin = o->multi_pin[parity];
+            if (pin.ptr) FRT_HIP_CHECK(hipStreamSynchronize(h->stream));      // (an earlier upload from this block may still be queued)
+            else if ((rc = pin.reserve(kNOctave * sizeof(OlaBatchArgs), kNOctave * sizeof(OlaBatchArgs)))) return rc;
+            memcpy(pin.ptr, deferred.data(), bytes);
+            FRT_HIP_CHECK(hipMemcpyAsync(o->multi_tab[parity].ptr, pin.ptr, bytes, hipMemcpyHostToDevice, h->stream));
+            held.assign((const char*)deferred.data(), (const char*)deferred.data() + bytes);      // only now: a failed upload leaves the table as `held` says
         }
         hipLaunchKernelGGL(ola_pair_multi_kernel, dim3((unsigned)at, best_groups, h->n_channels), dim3(kOwThreads), 0, h->stream,
                            o->multi_tab[parity].as<OlaBatchArgs>(), m);

@@ -6,7 +6,7 @@ oracle with the tolerance of their family's own test.  Sizes are the smallest th
 
 Blocks whose regrowth other tests already see, and which are therefore not repeated here:
   frt_specgram_push (chunk and pixel blocks)   test_widgets_gpu.py::test_spectrogram_stream_equals_host_chain (512 .. 3000 .. 512 .. 1)
-  frt_delay_push (the four slots)              test_gcc_gpu.py::test_delay_object_rings_equal_host_rings (512 .. 4096 .. 511, 12 rounds)
+  frt_delay_push (the four slots, delay.hip)   test_gcc_gpu.py::test_delay_object_rings_equal_host_rings (512 .. 4096 .. 511, 12 rounds)
   frt_levels_push                              test_levels_gpu.py, the "irregular" case (512 .. 8192 .. 20000, 255: above the 64 KB floor)
   frt_pitch_live_push                          test_pitchstream_gpu.py::test_ragged_chunks_and_a_stall (1-2 frames, 19 at once, 1-2)
 """
@@ -85,6 +85,46 @@ def test_iir_bank_filter_from_host_arrays(tabs):
         return bank.filter(x[:n])[0][0]
 
     small_large_small(call, lambda: IirBank(tabs["bdec"], tabs["adec"], boct, aoct, 1), (1024, 1 << 16, 1024))
+
+
+def test_iir_bank_graph_goes_when_only_the_pinned_blocks_move(tabs):
+    """The captured graph of filter_host (csrc/iir.hip) carries the addresses of both pinned blocks besides the device buffers'.
+    The device buffers grow geometrically, the pinned blocks to exactly the call's need, so a call can move the pinned blocks
+    alone; the graph of an earlier length must then be dropped, not replayed on the freed blocks.  One channel, 3 bands per
+    octave (packed length: 3 x the sum of the nine stage lengths), float64, sequential mode:
+
+      step 0  energies of [1, 2048] device samples: xbuf[1..8] hold 1024 .. 8 samples, more than the 550 .. 5 of a
+              1100-sample call (from 1024 samples alone xbuf[5] holds 32 and would move for 35, dropping the graph by the
+              device-buffer rule); xin, ypacked and the pinned blocks are not touched by a device-array call
+      1000    eager    xin 8000 B, ypacked 3 x 1998 = 5994 doubles, pin_in 8000 B, pin_out 47952 B
+      1024    eager    xin 8192 > 8000: grows to 1.5 x 8000 = 12000 B; ypacked 3 x 2044 = 6132 > 5994: grows to 1.5 x 5994 =
+                       8991 doubles; pin_in 8192 B, pin_out 49056 B (exactly the need)
+      1024    captured, launched
+      1024    replayed
+      1100    eager    xin 8800 <= 12000 B and ypacked 3 x 2199 = 6597 <= 8991 doubles stay; pin_in 8800 > 8192 B and
+                       pin_out 52776 > 49056 B are reallocated
+      1024    the graph of step 3 names the old pinned blocks: dropped, the call runs eagerly
+
+    Every call from zero state, against the same call on a handle of its own, bit for bit."""
+    import torch
+
+    from friture_amd.filter import IirBank
+    boct, aoct = list(tabs["boct_3"]), list(tabs["aoct_3"])
+    x = synth("noise", 1100, 10).astype(np.float64)
+
+    def make():
+        return IirBank(tabs["bdec"], tabs["adec"], boct, aoct, 1)
+
+    bank = make()
+    alphas, _ = dsp.band_smoothing_setup(3, 0.125)
+    bank.energies(torch.from_numpy(synth("noise", 2048, 11)[None, :]).cuda(), 1024, alphas)
+    torch.cuda.synchronize()
+    for step, n in enumerate((1000, 1024, 1024, 1024, 1100, 1024)):
+        bank.reset()
+        got, want = bank.filter(x[:n])[0][0], make().filter(x[:n])[0][0]
+        assert len(got) == len(want) == 27
+        for g, w in zip(got, want):
+            assert g.shape == w.shape and np.array_equal(g, w), (step, n)
 
 
 def test_decimate_multiple_state(hip, tabs):
