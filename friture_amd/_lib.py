@@ -156,6 +156,11 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
     "frt_delaybatch_readout": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_double, c_double, c_double,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "frt_resample_create": (c_int, [POINTER(c_void_p), c_int64, c_int64, c_int64, POINTER(c_double), c_int]),
+    "frt_resample_destroy": (None, [c_void_p]),
+    "frt_resample_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_resample_run": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                 c_int, c_int64]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

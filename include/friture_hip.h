@@ -628,6 +628,38 @@ int frt_specgram_batch(const double* norm, int streams, int64_t n_frames, int nb
                        const double* old_in, double* old_out, const uint32_t* lut256, uint32_t* pixels, int64_t col_offset,
                        int64_t ld_pixel);
 
+/* ---- R1: rational-ratio polyphase sample-rate converter (Resampler: recordings at other rates for the 48 kHz chains) -----
+ * The reference has no such component; this is the definition.  With g = gcd(rate_in, rate_out): L = rate_out / g,
+ * M = rate_in / g, Q = max(L, M), C = zeros * Q.  The prototype h[0 .. 2C] (host, float64) is a Kaiser-windowed sinc:
+ *   beta = 0.1102 (A - 8.7), dw = (A - 8) / (2.285 * 2C) rad/sample, fc = 0.5 / Q - dw / (4 pi) cycles/sample (the stop band
+ *   begins at the narrower Nyquist, so nothing folds back), h[n] = 2 fc sinc(2 fc (n - C)) kaiser(2C + 1, beta)[n], h *= L / sum(h)
+ * The output is zero-phase:
+ *   y[m] = sum_k h[C + m M - k L] x[k]   over every k with 0 <= C + m M - k L <= 2C;  x[k] = 0 outside the stream
+ * i.e. K = ceil((2C + 1) / L) taps per output, the first input being kb(m) = ceil((m M - C) / L), in 64-bit index arithmetic.
+ * After N inputs in total a stream that is not flushed has emitted max(0, ceil((N L - C) / M)) outputs (every tap of theirs has
+ * arrived), a flushed one ceil(N L / M) (later inputs are zeros).  The carried tail is the last K - 1 inputs: kb of the next
+ * output never reaches behind it.
+ * Arithmetic is float64 throughout (a float32 sample widens exactly, a float32 output is one rounding of the float64 sum), with
+ * fused multiply-adds.  One output is one chain acc = fma(h[..], x[kb + j], acc), j = 0 .. K - 1 from acc = 0: its order is
+ * fixed by the position in the period (m mod L) and by nothing else, so a stream cut into calls, run beside other streams or in
+ * another grid gives the same bits. */
+typedef struct frt_resample frt_resample;
+/* prototype: [2C + 1] HOST doubles; the handle keeps the table [K][L] (column q: the coefficients of the outputs m = q mod L) on
+ * the device.  FRT_ERR_INVALID, before any device call: L, M or C not positive, L == M (rate_in == rate_out), L and M with a
+ * common factor, L * K > 2^20 coefficients, streams outside 1 .. 65535. */
+int frt_resample_create(frt_resample** h, int64_t L, int64_t M, int64_t C, const double* prototype, int streams);
+void frt_resample_destroy(frt_resample* h);
+int frt_resample_set_stream(frt_resample* h, void* hip_stream);
+/* One call over all streams.  x: [streams][ld] float32 (x_dtype 0) or float64 (1), the n inputs first_in .. first_in + n - 1 of
+ * every stream (n = 0: x may be NULL).  tail_in: [streams][K - 1] doubles, the inputs before first_in, zeros before the stream's
+ * start (NULL: zeros, for first_in = 0 only); tail_out (or NULL): the same for the next call, a buffer distinct from tail_in.
+ * y: [streams][ldy] float32 (y_dtype 0) or float64 (1), the n_out outputs first_out .. first_out + n_out - 1; inputs from
+ * first_in + n on are zeros.  FRT_ERR_INVALID unless max(0, ceil((first_in L - C) / M)) <= first_out and first_out + n_out <=
+ * ceil((first_in + n) L / M): the caller chooses between the flushed and the unflushed count.  Host or device buffers in any
+ * mix (host ones are staged); one synchronisation at the end. */
+int frt_resample_run(frt_resample* h, const void* x, int x_dtype, int64_t n, int64_t ld, const double* tail_in, double* tail_out,
+                     int64_t first_in, int64_t first_out, int64_t n_out, void* y, int y_dtype, int64_t ldy);
+
 #ifdef __cplusplus
 }
 #endif
