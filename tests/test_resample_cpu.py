@@ -114,6 +114,106 @@ def test_carried_state_bookkeeping_gives_the_whole_bit_for_bit(designs, rate):
     assert np.array_equal(np.concatenate(out), whole)
 
 
+# ---- the design table of the GPU suite: which branches of the kernel each row reaches ----------------------------------------------
+
+def constants():
+    return H.kernel_constants((ROOT / "friture_amd" / "csrc" / "resample.hip").read_text())
+
+
+@pytest.mark.parametrize("row", H.ROWS, ids=lambda row: "-".join(map(str, row[0])))
+def test_design_row_reaches_its_class_at_the_kernels_constants(row):
+    """launch_plan restates frt_resample_create with kPeriods, kTapBlock and kCap read from resample.hip.  A retuned constant
+    that moves a row out of the branch it is in the table for fails here, naming the row and the entry: the row then needs
+    another (L, M, C), the GPU tests must not go on passing on a shape that no longer gets there."""
+    (L, M, C), want = row
+    periods, tap_block, cap = constants()
+    plan = H.launch_plan(L, M, C, periods, tap_block, cap)
+    print(f"L {L}, M {M}, C {C}: {plan}")
+    assert np.gcd(L, M) == 1 and L != M and plan["K"] == H.taps(L, C) >= 2 and L * plan["K"] <= MAX_COEFFICIENTS
+    for key, value in want.items():
+        assert plan[key] == value, (f"design row L {L}, M {M}, C {C} no longer reaches its class at kPeriods {periods}, kTapBlock "
+                                    f"{tap_block}, kCap {cap}: {key} is {plan[key]}, the row is there for {value}")
+    if not plan["direct"]:
+        assert 2 * ((plan["span"] + 2) // 2 * 2) <= cap, "the two LDS copies overrun kCap"
+    # the rows' input length: at least two whole tiles and a ragged third, whose last period is ragged too
+    n = H.row_length(L, M, plan["np"], periods)
+    outputs, tile = H.count(n, L, M, C, True), periods * plan["np"] * L
+    assert outputs > 2 * tile and outputs % tile and (L == 1 or outputs % L), (n, outputs, tile)
+    cuts = H.piece_cuts(n, plan["K"])
+    assert cuts[0] == 0 and cuts[-1] == n and list(cuts) == sorted(cuts) and len(cuts) == 8
+
+
+def test_the_classes_are_distinct_and_the_default_designs_reach_none_of_them():
+    """What the table adds: at the defaults (zeros 64, 48 kHz out) every design has K >= 129, the direct one has L = 1 and the
+    L = 1 designs read one LDS copy only."""
+    periods, tap_block, cap = constants()
+    for rate in H.RATES + (352800, 3840000):
+        r = Resampler(rate)
+        plan = H.launch_plan(r.L, r.M, r.C, periods, tap_block, cap)
+        assert plan["K"] == r.K >= 129 and plan["blocks"] >= 16 and plan["passes"] <= 2
+        assert not (plan["direct"] and r.L > 1) and (r.L > 1 or plan["parities"] <= {0})
+    assert len({row[0] for row in H.ROWS}) == len(H.ROWS) == 13
+    assert sum(1 for _, want in H.ROWS if want["direct"]) == 3
+
+
+def as_fraction(v):
+    """A long double (or Fraction) exactly."""
+    from fractions import Fraction
+    if isinstance(v, Fraction):
+        return v
+    hi = float(v)
+    return Fraction(hi) + Fraction(float(v - hi))
+
+
+@pytest.mark.parametrize("L,M,C", ((3, 2, 12), (5, 3, 3), (7, 9, 20)))
+def test_reference_and_bound(L, M, C):
+    """The extended-precision reference equals the exact rational one far inside the bound; the promised chain
+    acc = fma(c, x, acc), every fma rounded once (emulated in exact rationals), is within the bound; so is `gather`; a
+    mirrored prototype, a dropped edge tap and a duplicated one are far outside."""
+    from fractions import Fraction
+    rng = np.random.default_rng(L * 100 + M)
+    x, h, K = rng.standard_normal((2, 41)), rng.standard_normal(2 * C + 1), H.taps(L, C)
+    m1 = H.count(41, L, M, C, True)
+    ref, B = H.reference_and_bound(x, L, M, C, h, 0, m1)
+    exact, Bx = H.reference_and_bound(x, L, M, C, h, 0, m1, exact=True)
+    assert ref.shape == B.shape == exact.shape == (2, m1) and exact.dtype == object and isinstance(exact[0, 0], Fraction)
+    if H.EXTENDED:
+        assert ref.dtype == np.longdouble
+        for a, b, bound in zip(ref.ravel(), exact.ravel(), Bx.ravel()):
+            assert abs(as_fraction(a) - b) <= bound / 512               # 11 more bits, K + 1 roundings against K
+    for a, b in zip(B.ravel(), Bx.ravel()):
+        assert abs(as_fraction(a) - b) <= b / 2 ** 50               # 0 where every tap lies past the stream's end
+    assert Bx[0, 0] == Fraction(K, 2 ** 53 - K) * sum(abs(Fraction(h[C - k * L])) * abs(Fraction(x[0, k])) for k in range(C // L + 1))
+
+    def chain(hh, m, row, js):
+        kb, acc = -(-(m * M - C) // L), 0.0
+        for j in js:
+            k, i = kb + j, C + m * M - (kb + j) * L
+            if 0 <= i <= 2 * C and 0 <= k < x.shape[1]:
+                acc = float(Fraction(hh[i]) * Fraction(x[row, k]) + Fraction(acc))      # one rounding: a fused multiply-add
+        return acc
+
+    def chains(hh, js):
+        return np.array([[chain(hh, m, row, js) for m in range(m1)] for row in range(2)])
+
+    for kw in ({}, {"exact": True}):
+        r, b = (exact, Bx) if kw else (ref, B)
+        assert H.excess(chains(h, range(K)), r, b, **kw) <= 1.0
+        assert H.excess(chains(h, range(K - 1, -1, -1)), r, b, **kw) <= 1.0                 # any order of the K terms
+        assert H.excess(H.gather(x, L, M, C, h, 0, m1), r, b, **kw) <= 1.0
+        assert H.excess(chains(h[::-1], range(K)), r, b, **kw) > 1e6                        # mirrored
+        assert H.excess(chains(h, range(K - 1)), r, b, **kw) > 1e6                          # the last tap dropped
+        assert H.excess(chains(h, [0] + list(range(K))), r, b, **kw) > 1e6                  # the first tap twice
+        y32 = chains(h, range(K)).astype(np.float32)
+        assert H.excess(y32, r, b, **kw) <= 1.0
+        assert H.excess(np.nextafter(np.nextafter(y32, np.float32(np.inf)), np.float32(np.inf)), r, b, **kw) > 1.0
+    # a shifted stream: the same outputs from the samples behind k0 alone
+    part, Bp = H.reference_and_bound(x[:, 11:], L, M, C, h, m1 - 5, m1, k0=11)
+    full, _ = H.reference_and_bound(np.concatenate([np.zeros((2, 11)), x[:, 11:]], axis=1), L, M, C, h, m1 - 5, m1)
+    assert np.array_equal(part, full) and part.shape == Bp.shape == (2, 5)
+    assert H.reference_and_bound(x[:, :0], L, M, C, h, 0, 3)[0].shape == (2, 3)
+
+
 # ---- refusals, without a device -------------------------------------------------------------------------------------------------
 
 def test_refusals_are_raised_on_the_host():
