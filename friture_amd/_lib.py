@@ -161,6 +161,12 @@ SIGNATURES = {
     "frt_resample_set_stream": (c_int, [c_void_p, c_void_p]),
     "frt_resample_run": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                  c_int, c_int64]),
+    "frt_pcm_create": (c_int, [POINTER(c_void_p)]),
+    "frt_pcm_destroy": (None, [c_void_p]),
+    "frt_pcm_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_pcm_tile_frames": (c_int, [c_int, c_int]),
+    "frt_pcm_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int, c_int64,
+                               c_int64]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

@@ -660,6 +660,41 @@ int frt_resample_set_stream(frt_resample* h, void* hip_stream);
 int frt_resample_run(frt_resample* h, const void* x, int x_dtype, int64_t n, int64_t ld, const double* tail_in, double* tail_out,
                      int64_t first_in, int64_t first_out, int64_t n_out, void* y, int y_dtype, int64_t ldy);
 
+/* ---- R2: PCM ingest (recording.py: interleaved integer / float recordings, the data chunk of a WAV file) ------------------
+ * The reference has no such component (its audio arrives as float32 already); this is the definition.  A PCM buffer is
+ * n_frames_total frames of `channels` interleaved little-endian samples:
+ *   format  name  bytes                          value of a sample
+ *   0       u8    1                              (b - 128) * 2^-7
+ *   1       s16   2                              v * 2^-15
+ *   2       s24   3, packed, bit 23 the sign     v * 2^-23
+ *   3       s32   4                              v * 2^-31
+ *   4       f32   4                              the value itself
+ *   5       f64   8                              the value itself
+ * Full scale is [-1, 1).  Output row s, sample t is the value of channel select[s] of frame first_frame + t, as float32
+ * (y_dtype 0) or float64 (1).  Every value is exact in float64, those of u8, s16 and s24 in float32 too, so the output is
+ * defined to the bit: float64 is the exact value, float32 ONE round-to-nearest-even of it (s32: int -> float64 -> scale ->
+ * float32; f64: one conversion); float32 subnormals are kept; a NaN stays a NaN (its payload is not specified).
+ * One workgroup decodes a tile of frt_pcm_tile_frames(format, channels) frames — a multiple of 64 whose raw bytes are at
+ * most 32 KB, tiles counted from frame 0 — reading the tile's bytes once, every channel of them: channels that `select`
+ * leaves out are still read (one contiguous span is the point), and no byte outside the requested frames is. */
+typedef struct frt_pcm frt_pcm;
+int frt_pcm_create(frt_pcm** h);
+void frt_pcm_destroy(frt_pcm* h);
+int frt_pcm_set_stream(frt_pcm* h, void* hip_stream);
+/* pure host: frames per workgroup, or FRT_ERR_INVALID (format outside 0 .. 5, channels outside 1 .. 64) */
+int frt_pcm_tile_frames(int format, int channels);
+/* data: n_frames_total * channels * width bytes, host or device, at ANY byte address.  select: HOST array of n_select channel
+ * indices (repeats and any order allowed).  y: [n_select][ldy], host or device; columns from n_frames on are left alone.
+ * Buffers in any mix.  Host data goes up in slabs of whole tiles of at most slab_bytes (0: 64 MB) through two page-locked
+ * blocks, slab k + 1 being copied while slab k is in flight; a host y comes back through two more, slab k - 1 being copied
+ * out while slab k runs (the handle owns four page-locked blocks); data and y both on the device: one launch.  A handle serves
+ * one call at a time.  The result is the same to the bit for every slab_bytes.  One synchronisation at the end.
+ * FRT_ERR_INVALID, before any device call: an unknown format or y_dtype, channels outside 1 .. 64, n_select outside
+ * 1 .. 65535, a select entry outside [0, channels), frames outside [0, n_frames_total], ldy < n_frames.  n_frames = 0 does
+ * nothing. */
+int frt_pcm_decode(frt_pcm* h, const void* data, int format, int channels, int64_t n_frames_total, int64_t first_frame,
+                   int64_t n_frames, const int32_t* select, int n_select, void* y, int y_dtype, int64_t ldy, int64_t slab_bytes);
+
 #ifdef __cplusplus
 }
 #endif

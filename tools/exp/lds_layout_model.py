@@ -20,6 +20,12 @@ GROUPS = {
     "write_b64": ([list(range(16 * g, 16 * g + 16)) for g in range(4)], 32, 8),
     "read_b128": (R128 + [[l + 32 for l in g] for g in R128], 64, 16),
     "write_b128": ([list(range(8 * g, 8 * g + 8)) for g in range(8)], 32, 16),
+    "read_b32": ([list(range(0, 32)), list(range(32, 64))], 32, 4),
+    "write_b32": ([list(range(0, 32)), list(range(32, 64))], 32, 4),
+    # ds_write2_b32: the guide gives its cycles (6, those of ds_write_b64) and not its lane groups.  Modelled both ways: as two
+    # ds_write_b32 (each dword of the pair an access of its own: "write_b32" on either address), and, here, as ds_write_b64's
+    # groups with the two dwords of a lane serviced together (an address entry is then the pair of byte addresses)
+    "write2_b32": ([list(range(16 * g, 16 * g + 16)) for g in range(4)], 32, 4),
 }
 
 
@@ -30,11 +36,11 @@ def degree(kind: str, addrs) -> int:
     for g in groups:
         banks: dict = {}
         for lane in g:
-            a = addrs[lane]
-            if a is None:
+            if addrs[lane] is None:
                 continue
-            for d in range(width // 4):
-                banks.setdefault((a // 4 + d) % nbanks, set()).add(a)
+            for a in (addrs[lane] if isinstance(addrs[lane], tuple) else (addrs[lane],)):
+                for d in range(width // 4):
+                    banks.setdefault((a // 4 + d) % nbanks, set()).add(a)
         for s in banks.values():
             worst = max(worst, len(s))
     return worst
@@ -190,8 +196,60 @@ KERNELS = {"stft_kernel N=1024": stft_wave512, "ola_pair_kernel": ola_pair, "stf
 # layouts that were replaced, kept so that the model can be seen to tell them apart (not asserted conflict free)
 BEFORE = {"stft_kernel N=1024, one pad slot per 8 points": stft_wave512_padded}
 
+
+# ---- pcm_decode_kernel (csrc/pcm.hip): the raw bytes of a tile of interleaved frames, read back one frame per lane --------------
+PCM_WIDTH = {"u8": 1, "s16": 2, "s24": 3, "s32": 4, "f32": 4, "f64": 8}
+PCM_TILE_BYTES = 32768
+
+
+def pcm_phys(D):                              # pcm.hip pcm_phys: one pad dword behind every 32 logical dwords, one more behind every 1024
+    return D + (D >> 5) + (D >> 10)
+
+
+def pcm_flat(D):                              # no pads: what the layout replaced
+    return D
+
+
+def pcm_tile_frames(fmt, channels):
+    return PCM_TILE_BYTES // (channels * PCM_WIDTH[fmt]) // 64 * 64
+
+
+def pcm_decode(fmt, channels, mis=0, phys=pcm_phys):
+    """Logical byte `mis` + r * C * width + c * width of the image is sample (frame r, channel c); lane l of a wavefront reads
+    frame 64 k + l.  An aligned sample (mis a multiple of the width; never s24) is read as its own dword(s), any other as the
+    dwords D, D + 1 (and D + 2 for f64) that hold it, each a ds_read_b32.  The fill stores every global 16-byte granule as four
+    dwords q .. q + 3 from q = phys(4 g): the compiler emits two ds_write2_b32 (q, q + 1 and q + 2, q + 3).  "fill write": each
+    dword an access of its own (as two ds_write_b32); "fill write, pairs together": the two dwords of a lane in one access with
+    ds_write_b64's lane groups, where 16 lanes at a 16-byte stride reach 16 of the 32 banks, so 2 is the floor for any layout.
+    Worst degree over every chunk of the tile, channel and dword."""
+    w = PCM_WIDTH[fmt]
+    frame, F = channels * w, pcm_tile_frames(fmt, channels)
+    aligned = w != 3 and mis % w == 0
+    n = (1 if w <= 4 else 2) if aligned else (2 if w <= 4 else 3)
+    read = 1
+    for c in range(channels):
+        for d in range(n):
+            for k in range(F // 64):
+                read = max(read, degree("read_b32", [4 * phys(((mis + (64 * k + l) * frame + c * w) >> 2) + d) for l in range(64)]))
+    granules = (F * frame + 15) // 16
+    write = max(degree("write_b32", [4 * (phys(4 * (64 * k + l)) + i) if 64 * k + l < granules else None for l in range(64)])
+                for k in range((granules + 63) // 64) for i in range(4))
+    pairs = max(degree("write2_b32", [(4 * (phys(4 * (64 * k + l)) + i), 4 * (phys(4 * (64 * k + l)) + i + 1)) if 64 * k + l < granules else None
+                                       for l in range(64)]) for k in range((granules + 63) // 64) for i in (0, 2))
+    return {"decode read": read, "fill write": write, "fill write, pairs together": pairs}
+
+
+# (format, channels, address of the buffer mod 16): the shapes DESIGN.md R2 quotes
+PCM_CASES = [("u8", 1, 0), ("u8", 2, 0), ("s16", 1, 0), ("s16", 2, 0), ("s16", 2, 1), ("s16", 8, 0), ("s24", 1, 0), ("s24", 2, 0), ("s24", 8, 0),
+             ("s24", 6, 0), ("s32", 2, 0), ("s32", 16, 0), ("s32", 32, 0), ("s32", 32, 2), ("s32", 64, 0), ("f32", 2, 0), ("f64", 1, 0),
+             ("f64", 2, 0), ("f64", 8, 0), ("f64", 16, 0), ("f64", 32, 0), ("f64", 32, 4), ("f64", 64, 0)]
+
 if __name__ == "__main__":
     for name, fn in list(KERNELS.items()) + list(BEFORE.items()):
         print(name)
         for k, v in fn().items():
             print(f"    {k:24s} worst conflict degree {v}")
+    print("pcm_decode_kernel: format x channels (buffer address mod 16): decode read, fill write (dwords apart, pairs together); decode read without the pads")
+    for fmt, channels, mis in PCM_CASES:
+        res, flat = pcm_decode(fmt, channels, mis), pcm_decode(fmt, channels, mis, pcm_flat)
+        print(f"    {fmt:3s} x {channels:2d} ({mis:2d})   {res['decode read']:2d}  {res['fill write']:2d} {res['fill write, pairs together']:2d}     {flat['decode read']:2d}")
