@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 import sys
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libfriture_hip.so"
@@ -167,6 +167,11 @@ SIGNATURES = {
     "frt_pcm_tile_frames": (c_int, [c_int, c_int]),
     "frt_pcm_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int, c_int64,
                                c_int64]),
+    "frt_pcmenc_create": (c_int, [POINTER(c_void_p)]),
+    "frt_pcmenc_destroy": (None, [c_void_p]),
+    "frt_pcmenc_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_pcmenc_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int,
+                                  c_uint64, c_void_p, c_void_p, c_int64]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

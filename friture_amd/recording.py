@@ -7,7 +7,12 @@ A PCM buffer is frames of `channels` interleaved little-endian samples; FORMATS 
 exact value, the float32 output one round-to-nearest-even of it.  The raw bytes go to the device once (host data in slabs
 through page-locked memory); one kernel de-interleaves, selects channels, sign-extends and scales.  wav_info reads a WAV
 header without the `wave` module (which refuses WAVE_FORMAT_EXTENSIBLE and float files on older interpreters); load_wav maps
-the file, decodes it and brings it to SAMPLING_RATE.  There is no CPU fallback: decode_pcm goes to the HIP library."""
+the file, decodes it and brings it to SAMPLING_RATE.  There is no CPU fallback: decode_pcm goes to the HIP library.
+
+The way out is the mirror (pcmenc.hip, frt_pcmenc_*; include/friture_hip.h, R3): encode_pcm routes rows to output channels,
+rounds half to even, saturates (counting what it clipped), optionally dithers, and interleaves on the device; wav_header and
+save_wav write the file that wav_info and load_wav read back; player_route and mode="player" are the routing and the int16
+block arithmetic of the reference's playback (friture/playback/player.py:148-182)."""
 from __future__ import annotations
 
 import ctypes
@@ -170,6 +175,177 @@ def _handle():
         return _shared
 
 
+# ---- the way out: planar float rows to interleaved PCM (pcmenc.hip, frt_pcmenc_*; the definition: friture_hip.h, R3) ------------
+
+MAX_ROWS = 65535
+MAX_FRAME_INDEX = 1 << 50
+MODES = {"nearest": 0, "player": 1}
+
+
+class EncodedPcm(NamedTuple):
+    data: object          # 1-D uint8: frames of `channels` interleaved little-endian samples
+    clipped: np.ndarray   # int64 [channels]: samples per output channel that were out of range or NaN
+
+
+def player_route(n_rows, out_channels):
+    """The route of the reference's playback block (friture/playback/player.py:161-171): one row goes to every output;
+    otherwise row c goes to output c and the outputs beyond the rows are silent (-1)."""
+    n_rows, out_channels = operator.index(n_rows), operator.index(out_channels)
+    if n_rows < 1 or out_channels < 1:
+        raise ValueError(f"{n_rows} rows to {out_channels} outputs")
+    return [0] * out_channels if n_rows == 1 else [c if c < n_rows else -1 for c in range(out_channels)]
+
+
+def _rows_of(x):
+    """(x as [S, T], is_np) of the float rows a numpy array or CUDA tensor holds."""
+    is_np = isinstance(x, np.ndarray)
+    if not is_np and not (type(x).__module__.startswith("torch") and x.is_cuda):
+        raise TypeError(f"samples: a numpy array or a CUDA tensor, got {type(x).__name__}")
+    if x.ndim not in (1, 2):
+        raise ValueError(f"expected [S, T] or [T], got {tuple(x.shape)}")
+    if str(x.dtype).split(".")[-1] not in ("float32", "float64"):
+        raise TypeError(f"samples must be float32 or float64, got {x.dtype}")
+    return (x[None] if x.ndim == 1 else x), is_np
+
+
+def _check_route(route, channels, n_rows):
+    try:
+        rt = np.arange(n_rows, dtype=np.int64) if route is None else np.array([operator.index(r) for r in route], np.int64)
+    except TypeError as e:
+        raise ValueError(f"route {route!r}: a sequence of integer row indices (-1: silence)") from e
+    if not 1 <= rt.size <= MAX_CHANNELS:
+        raise ValueError(f"channels {rt.size} (1 .. {MAX_CHANNELS})")
+    if channels is not None:
+        if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or int(channels) != rt.size:
+            raise ValueError(f"channels {channels!r} for a route of {rt.size} entries")
+    if rt.min() < -1 or rt.max() >= n_rows:
+        raise ValueError(f"route {rt.tolist()} of {n_rows} rows (-1: silence)")
+    return np.ascontiguousarray(rt, np.int32)
+
+
+def _destination(out, n_bytes):
+    """(out, on the host?) of a caller's destination: a writable 1-D uint8 numpy array (np.memmap) or CUDA tensor of n_bytes."""
+    if type(out).__module__.startswith("torch"):
+        import torch
+        if not out.is_cuda or out.dtype != torch.uint8 or out.ndim != 1 or (out.numel() > 1 and out.stride(0) != 1):
+            raise TypeError(f"out: a 1-D unit-stride CUDA uint8 tensor, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        host = False
+    elif isinstance(out, np.ndarray):
+        if out.dtype != np.uint8 or out.ndim != 1 or (out.size > 1 and out.strides[0] != 1) or not out.flags.writeable:
+            raise TypeError(f"out: a writable 1-D unit-stride uint8 array, got {out.dtype} {out.shape}")
+        host = True
+    else:
+        raise TypeError(f"out: a numpy uint8 array, np.memmap or CUDA uint8 tensor, got {type(out).__name__}")
+    if int(out.shape[0]) != n_bytes:
+        raise ValueError(f"out holds {int(out.shape[0])} bytes, the encoding has {n_bytes}")
+    return out, host
+
+
+def encode_pcm(x, fmt, route=None, channels=None, frame0=0, dither=False, seed=0, mode="nearest", to=None, out=None, slab_bytes=None):
+    """EncodedPcm(data, clipped): the rows x [S, T] (or [T]; float32 / float64, a numpy array or a CUDA tensor, read in place
+    whatever the row stride) as T frames of interleaved little-endian samples of format `fmt`, the inverse of decode_pcm.
+    route[c]: the row that output channel c carries, -1 for silence, repeats and any order allowed (None: every row in order);
+    channels, when given, is len(route).  Integer formats round half to even and saturate; clipped[c] counts the samples of
+    channel c that were out of range or NaN.  dither=True adds triangular dither of +-1 LSB before the rounding, a pure function
+    of (seed, frame0 + frame, channel): a recording cut into pieces encodes to the same bytes when each piece is given its
+    frame0.  mode="player" (s16, no dither) is the reference's output block, trunc(32767 * clip(v, -1, 1)).
+    data is 1-D uint8: a numpy array for numpy rows, a CUDA tensor for a tensor (to="host": a numpy array, the bytes coming down
+    in slabs — the float rows never exist on the host; to="cuda": a CUDA tensor from numpy rows), or `out`, a writable 1-D uint8
+    numpy array, np.memmap or CUDA tensor of exactly T * channels * width bytes at any byte offset.  Host buffers move in slabs
+    of at most slab_bytes (None: 64 MB); the result does not depend on it.  Calls from several threads share one set of staging
+    buffers and run one after the other."""
+    if not isinstance(fmt, str) or fmt not in FORMATS:
+        raise ValueError(f"format {fmt!r} (one of {', '.join(FORMATS)})")
+    code, width = FORMATS[fmt]
+    x, is_np = _rows_of(x)
+    S, T = int(x.shape[0]), int(x.shape[1])
+    if not 1 <= S <= MAX_ROWS:
+        raise ValueError(f"{S} rows (1 .. {MAX_ROWS})")
+    rt = _check_route(route, channels, S)
+    C = int(rt.size)
+    frame0 = operator.index(frame0)
+    if frame0 < 0 or frame0 + T > MAX_FRAME_INDEX:
+        raise ValueError(f"frame0 {frame0} with {T} frames (0 .. 2^50)")
+    if mode not in MODES:
+        raise ValueError(f"mode {mode!r} (one of {', '.join(MODES)})")
+    if not isinstance(dither, (bool, np.bool_)):
+        raise TypeError(f"dither {dither!r} (True or False)")
+    dither = bool(dither)
+    if dither and code >= 4:
+        raise ValueError(f"dither with the float format {fmt}")
+    if mode == "player" and (fmt != "s16" or dither):
+        raise ValueError(f"mode 'player' is for s16 without dither, got {fmt}{' with dither' if dither else ''}")
+    seed = operator.index(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed {seed} (0 .. 2^64 - 1)")
+    if to not in (None, "host", "cuda"):
+        raise ValueError(f"to={to!r} (None, 'host' or 'cuda')")
+    slab = 0 if slab_bytes is None else int(slab_bytes)
+    if slab < 0:
+        raise ValueError(f"slab_bytes {slab_bytes!r}")
+    n_bytes = T * C * width
+    if out is not None:
+        if to is not None:
+            raise ValueError("give `out` or `to`, not both")
+        out, host_out = _destination(out, n_bytes)
+        if not is_np and not host_out and out.device != x.device:
+            raise ValueError(f"out is on {out.device}, the rows are on {x.device}")
+    else:
+        host_out = is_np if to is None else to == "host"
+    clipped = np.zeros(C, np.int64)
+    if is_np and host_out and out is None:
+        out = np.empty(n_bytes, np.uint8)
+    h, vp = _encoder(), ctypes.c_void_p
+
+    def call(data):
+        src, addr, x_dtype, strides = _batchio.source(x, strided=True)
+        if S > 1 and strides[0] < T:                            # rows that overlap (an expanded tensor): read a copy
+            src, addr, x_dtype, strides = _batchio.source(x, strided=False)
+        with h.lock:
+            _lib.check(h.lib.frt_pcmenc_set_stream(h.h, None))
+            _lib.check(h.lib.frt_pcmenc_encode(h.h, vp(addr) if T else None, x_dtype, S, int(strides[0]) if S > 1 else max(T, 1), T,
+                                               frame0, vp(rt.ctypes.data), C, code, MODES[mode], int(dither), seed,
+                                               vp(_batchio.ptr(data)) if T else None, vp(clipped.ctypes.data), slab))
+        del src                                                 # a copy lives until the call has synchronised
+
+    if is_np and host_out:
+        call(out)
+        return EncodedPcm(out, clipped)
+    import torch
+    anchor = x if not is_np else out                            # the tensor whose device and stream the call joins, if there is one
+    with _batchio.null_stream(anchor, anchor is None) as dev:
+        if out is None:
+            out = np.empty(n_bytes, np.uint8) if host_out else torch.empty(n_bytes, dtype=torch.uint8, device=dev)
+        call(out)
+    return EncodedPcm(out, clipped)
+
+
+class _Encoder:
+    """One frt_pcmenc object behind a lock: encode_pcm's page-locked slabs and device staging, as _Handle is decode_pcm's."""
+
+    def __init__(self):
+        self.lock = threading.Lock()
+        self.lib = _lib.init()
+        self.h = ctypes.c_void_p()
+        _lib.check(self.lib.frt_pcmenc_create(ctypes.byref(self.h)))
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.frt_pcmenc_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+
+_shared_encoder = None
+
+
+def _encoder():
+    global _shared_encoder
+    with _shared_lock:
+        if _shared_encoder is None:
+            _shared_encoder = _Encoder()
+        return _shared_encoder
+
+
 # ---- WAV files ------------------------------------------------------------------------------------------------------------------
 
 _GUID_TAIL = bytes.fromhex("000000001000800000aa00389b71")          # KSDATAFORMAT_SUBTYPE_*: the tag, then these 14 bytes
@@ -255,3 +431,69 @@ def load_wav(path, select=None, dtype=np.float32, rate=SAMPLING_RATE, to="cuda",
         from .resample import Resampler
         samples = Resampler(info.rate, int(rate)).run(samples, dtype=name).y
     return Recording(samples, info.rate, info)
+
+
+def _chunk(cid, body):
+    return cid + struct.pack("<I", len(body)) + body + (b"\0" if len(body) & 1 else b"")
+
+
+def wav_header(fmt, channels, rate, n_frames):
+    """The bytes of a RIFF/WAVE file in front of its samples, for n_frames frames of `channels` samples of format `fmt`: a
+    plain `fmt ` chunk (tag 1) for u8 / s16 with at most 2 channels, otherwise WAVE_FORMAT_EXTENSIBLE with the PCM or IEEE-float
+    sub-format, valid bits equal to the container's and channel mask 0; a `fact` chunk for the float formats; then the `data`
+    chunk's header.  The file is these bytes, the n_frames * channels * width sample bytes and, when that count is odd, one
+    pad byte.  ValueError when the RIFF size would pass 2^32 - 1 (RF64 is out of scope, as on the way in)."""
+    code, width, channels = _check_format(fmt, channels)
+    rate, n_frames = operator.index(rate), operator.index(n_frames)
+    if not 1 <= rate < 1 << 32:
+        raise ValueError(f"rate {rate}")
+    if n_frames < 0:
+        raise ValueError(f"{n_frames} frames")
+    block, bits, tag = channels * width, 8 * width, 3 if code >= 4 else 1
+    if block * rate >= 1 << 32:
+        raise ValueError(f"{block * rate} bytes per second do not fit the fmt chunk")
+    body = struct.pack("<HHIIHH", tag, channels, rate, rate * block, block, bits)
+    if not (fmt in ("u8", "s16") and channels <= 2):
+        body = struct.pack("<H", 0xFFFE) + body[2:] + struct.pack("<HHI", 22, bits, 0) + struct.pack("<H", tag) + _GUID_TAIL
+    chunks = _chunk(b"fmt ", body)
+    data = n_frames * block
+    if tag == 3:
+        if n_frames >= 1 << 32:
+            raise ValueError(f"{n_frames} frames do not fit a RIFF file (RF64 is not supported)")
+        chunks += _chunk(b"fact", struct.pack("<I", n_frames))
+    riff = 4 + len(chunks) + 8 + data + (data & 1)
+    if riff > 0xFFFFFFFF:
+        raise ValueError(f"{data} bytes of samples do not fit a RIFF file (RF64 is not supported)")
+    return b"RIFF" + struct.pack("<I", riff) + b"WAVE" + chunks + b"data" + struct.pack("<I", data)
+
+
+def save_wav(path, samples, rate=SAMPLING_RATE, fmt="s16", route=None, dither=None, seed=0, slab_bytes=None):
+    """Writes the rows `samples` [S, T] (or [T]; a numpy array or a CUDA tensor) as a WAV file of format `fmt` and returns its
+    wav_info: wav_header, the file sized, its data region mapped with np.memmap and filled by encode_pcm (a CUDA tensor comes
+    down as encoded bytes in slabs; the float rows never exist on the host).  route: as for encode_pcm, one output channel per
+    entry.  dither: None means ON for u8 and s16 and OFF for every other format — say dither=False for the plain rounding of
+    a 16-bit file; seed: the dither's.  When the encode fails the file is removed: no header over zeros stays behind."""
+    path = os.fspath(path)
+    x, _ = _rows_of(samples)
+    if not isinstance(fmt, str) or fmt not in FORMATS:
+        raise ValueError(f"format {fmt!r} (one of {', '.join(FORMATS)})")
+    rt = _check_route(route, None, int(x.shape[0]))
+    if dither is None:
+        dither = fmt in ("u8", "s16")
+    T, width = int(x.shape[1]), FORMATS[fmt][1]
+    head = wav_header(fmt, int(rt.size), rate, T)
+    n_bytes = T * int(rt.size) * width
+    with open(path, "wb") as f:
+        f.write(head)
+        f.truncate(len(head) + n_bytes + (n_bytes & 1))
+    if n_bytes:
+        data = np.memmap(path, np.uint8, "r+", offset=len(head), shape=(n_bytes,))
+        try:
+            encode_pcm(x, fmt, route=rt.tolist(), dither=dither, seed=seed, out=data, slab_bytes=slab_bytes)
+            data.flush()
+        except BaseException:                   # no file of zeros with a valid header is left behind
+            del data
+            os.remove(path)
+            raise
+        del data
+    return wav_info(path)

@@ -695,6 +695,51 @@ int frt_pcm_tile_frames(int format, int channels);
 int frt_pcm_decode(frt_pcm* h, const void* data, int format, int channels, int64_t n_frames_total, int64_t first_frame,
                    int64_t n_frames, const int32_t* select, int n_select, void* y, int y_dtype, int64_t ldy, int64_t slab_bytes);
 
+/* ---- R3: PCM export (recording.py encode_pcm / save_wav: planar float rows to interleaved PCM, the mirror of R2) ---------
+ * Input: x[n_rows][ldx], float32 (x_dtype 0) or float64 (1), host or device.  Output: n_frames frames of `channels`
+ * interleaved little-endian samples of one of R2's six formats, n_frames * channels * width bytes at ANY byte address, host
+ * or device.  route[c], c in [0, channels), a HOST array: the row that output channel c carries, -1 for silence; repeats
+ * and any order allowed (the mirror of `select`).
+ * An integer format of b bits (u8 8, s16 16, s24 24, s32 32), v the sample converted exactly to float64 (mode 0):
+ *   t = v * 2^(b-1)                      exact in float64
+ *   t = t + d                            with dither only: one float64 addition, d below
+ *   r = rint(t)                          round half to even
+ *   q = clamp(r, -2^(b-1), 2^(b-1) - 1)  a NaN encodes as q = 0
+ * u8 stores q + 128, s24 the low three bytes of q.  A silent channel stores 0 (u8: 128).  clipped[c], an int64 HOST array of
+ * `channels` entries (or NULL): the call ADDS, per output channel, the number of samples whose r lay outside the range or was
+ * NaN; silent channels and the float formats add nothing.
+ * f32 from float32 and f64 from float64 are bit copies (a NaN stays a NaN, its payload is not specified), f64 from float32
+ * the exact widening, f32 from float64 ONE round-to-nearest-even (subnormals kept, overflow to infinity); silence is +0.0.
+ * This inverts R2's scale: encode(decode(raw)) == raw for every byte string of an integer format with float64 rows, and
+ * with float32 rows for u8, s16 and s24 (s32 through float32 does not round-trip).
+ * mode 1 ("player", s16 only, no dither): q = (int16) trunc(32767 * min(max(v, -1), 1)), the float64 product truncated toward
+ * zero — the statements of friture/playback/player.py:173-177; a NaN gives 0; clipped[c] counts |v| > 1 and NaN.
+ * Dither (integer formats, mode 0): Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9,
+ * 0xBB67AE85) on the counter (f & 0xffffffff, f >> 32, c, 0), f = frame0 + i the absolute frame index and c the OUTPUT
+ * channel, with the key (seed & 0xffffffff, seed >> 32).  With outputs o0 .. o3,
+ *   d = ((int)(o0 >> 8) - (int)(o1 >> 8)) * 2^-24
+ * a triangular density on (-1, 1) LSB, exact in float64.  The bytes depend on (x, route, format, seed, frame0) only: not on
+ * tile, slab, launch shape or how a recording is cut into calls.
+ * One workgroup encodes a tile of frt_pcm_tile_frames(format, channels) frames, tiles counted from frame 0 of the output;
+ * no byte outside the n_frames * channels * width bytes of dst is written. */
+typedef struct frt_pcmenc frt_pcmenc;
+int frt_pcmenc_create(frt_pcmenc** h);             /* allocates nothing on the device */
+void frt_pcmenc_destroy(frt_pcmenc* h);            /* no device call for a handle that never reached the device */
+int frt_pcmenc_set_stream(frt_pcmenc* h, void* hip_stream);
+/* A host x (the rows the route names, once each) or a host dst goes through the handle's page-locked blocks in slabs of whole
+ * tiles of at most slab_bytes encoded bytes (0: 64 MB): the host copy of slab k + 1's rows and of slab k - 1's bytes run while
+ * slab k is in flight (uploads, kernels and downloads share the handle's one stream and run one after the other there); x and
+ * dst both on the device: one launch.  The clip counts are added up on the device per workgroup and then, with atomic adds, into
+ * a [16][64] int64 table (row: workgroup mod 16) that the call zeroes, reads back once at the end (8 KB) and sums on the host.
+ * A handle serves one call at a time.  The result is the same to the bit for every slab_bytes.  One synchronisation
+ * at the end.  FRT_ERR_INVALID, before any device call: a null handle, an unknown format, x_dtype, mode or dither, channels
+ * outside 1 .. 64, n_rows outside 1 .. 65535, a route entry outside [-1, n_rows), n_frames < 0, frame0 < 0, frame0 + n_frames
+ * > 2^50, ldx < n_frames, slab_bytes < 0, mode 1 with a format other than s16 or with dither, dither with a float format.
+ * n_frames = 0 does nothing. */
+int frt_pcmenc_encode(frt_pcmenc* h, const void* x, int x_dtype, int n_rows, int64_t ldx, int64_t n_frames, int64_t frame0,
+                      const int32_t* route, int channels, int format, int mode, int dither, uint64_t seed, void* dst,
+                      int64_t* clipped, int64_t slab_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -244,6 +244,59 @@ PCM_CASES = [("u8", 1, 0), ("u8", 2, 0), ("s16", 1, 0), ("s16", 2, 0), ("s16", 2
              ("s24", 6, 0), ("s32", 2, 0), ("s32", 16, 0), ("s32", 32, 0), ("s32", 32, 2), ("s32", 64, 0), ("f32", 2, 0), ("f64", 1, 0),
              ("f64", 2, 0), ("f64", 8, 0), ("f64", 16, 0), ("f64", 32, 0), ("f64", 32, 4), ("f64", 64, 0)]
 
+# ---- pcm_encode_kernel (csrc/pcmenc.hip): the encoded bytes of a tile, written one sample per lane, read back as 16-byte granules -----
+def pcm_encode(fmt, channels, mis=0, phys=pcm_phys):
+    """The mirror of pcm_decode with the two sides exchanged; pcmenc.hip's pcmenc_phys is pcm_phys.  Logical byte `mis` + r * C *
+    width + c * width of the image is sample (frame r, channel c); lane l of a wavefront writes frame 64 k + l.  A sample whose
+    address is a multiple of min(width, 4) is written at its natural width — one byte, one 16-bit or one 32-bit store, two
+    32-bit stores for f64 — an s24 sample as a 16-bit store at the even address of its three and a byte store at the other
+    end, any other sample byte by byte.  The guide gives lane groups and banks for ds_write_b32 and
+    wider, not for the 8- and 16-bit stores: they are modelled with ds_write_b32's (two groups of 32 lanes, 32 banks), in two
+    ways, as the ds_write2_b32 of pcm_decode is.  "encode write": lanes that store into ONE dword count as one address (a
+    bank serves a dword); "encode write, bytes apart": every byte address counts as its own, the pessimistic reading.  "drain
+    read": a thread reads the four dwords q .. q + 3 of a granule from q = phys(4 g), thread t on granule 256 j + t, each dword
+    an access of its own (ds_read_b32: q is not a multiple of four, so the four are no ds_read_b128).  Worst degree over every
+    chunk of the tile, channel and byte or dword of the sample."""
+    w = PCM_WIDTH[fmt]
+    frame, F = channels * w, pcm_tile_frames(fmt, channels)
+    natural = w != 3 and mis % min(w, 4) == 0
+    # per store instruction, the offset of its first byte in the sample at logical byte L
+    if w == 3:                 # a 16-bit store at the even address of the three, a byte store at the other end
+        stores = [lambda L: L & 1, lambda L: 2 - 2 * (L & 1)]
+    elif natural:
+        stores = [lambda L, i=i: 4 * i for i in range(max(1, w // 4))]
+    else:
+        stores = [lambda L, i=i: i for i in range(w)]
+    together = apart = 1
+    for c in range(channels):
+        for off in stores:
+            for k in range(F // 64):
+                at = [L + off(L) for L in (mis + (64 * k + l) * frame + c * w for l in range(64))]
+                byte = [4 * phys(a >> 2) + (a & 3) for a in at]
+                together = max(together, degree("write_b32", [b & ~3 for b in byte]))
+                apart = max(apart, _degree_by_byte("write_b32", byte))
+    first, granules = (mis + 15) // 16, (mis + F * frame) // 16              # the whole granules of the image: [first, granules)
+    read = max(degree("read_b32", [4 * (phys(4 * (first + 64 * k + l)) + i) if first + 64 * k + l < granules else None for l in range(64)])
+               for k in range((granules - first + 63) // 64) for i in range(4))
+    return {"encode write": together, "encode write, bytes apart": apart, "drain read": read}
+
+
+def _degree_by_byte(kind, addrs):
+    """degree() with sub-dword accesses: the bank is the dword's, every distinct byte address an access of its own."""
+    groups, nbanks, _ = GROUPS[kind]
+    worst = 1
+    for g in groups:
+        banks: dict = {}
+        for lane in g:
+            if addrs[lane] is not None:
+                banks.setdefault((addrs[lane] // 4) % nbanks, set()).add(addrs[lane])
+        worst = max([worst] + [len(s) for s in banks.values()])
+    return worst
+
+
+PCMENC_CHANNELS = (1, 2, 3, 6, 8, 32, 64)
+PCMENC_MIS = (0, 1, 3, 8)
+
 if __name__ == "__main__":
     for name, fn in list(KERNELS.items()) + list(BEFORE.items()):
         print(name)
@@ -253,3 +306,9 @@ if __name__ == "__main__":
     for fmt, channels, mis in PCM_CASES:
         res, flat = pcm_decode(fmt, channels, mis), pcm_decode(fmt, channels, mis, pcm_flat)
         print(f"    {fmt:3s} x {channels:2d} ({mis:2d})   {res['decode read']:2d}  {res['fill write']:2d} {res['fill write, pairs together']:2d}     {flat['decode read']:2d}")
+    print("pcm_encode_kernel: format x channels (destination address mod 16): encode write (a dword one address, bytes apart), drain read; encode write without the pads")
+    for fmt in PCM_WIDTH:
+        for channels in PCMENC_CHANNELS:
+            for mis in PCMENC_MIS:
+                res, flat = pcm_encode(fmt, channels, mis), pcm_encode(fmt, channels, mis, pcm_flat)
+                print(f"    {fmt:3s} x {channels:2d} ({mis:2d})   {res['encode write']:2d} {res['encode write, bytes apart']:2d}  {res['drain read']:2d}     {flat['encode write']:2d}")
