@@ -15,9 +15,10 @@
 // therefore computed independently (time-parallel) and the carried state is the last 10 (40) INPUTS of each stage.
 //
 // Kernels of one call (all on the object's stream):
-//   levels_front_kernel  one read of the input: per chunk max|x| and the RMS dot (exp_smooth_rows_kernel's products and
-//                        order: 64 strided lanes, then a __shfl_down tree); the squaring and the first S decimation stages
-//                        in LDS, with a halo of 10 (2^S - 1) samples; the stage-S signal to HBM
+//   levels_front_kernel  one read of the input: per chunk max|x| (NaN when a sample is, as numpy's max) and the RMS dot
+//                        (exp_smooth_rows_kernel's products and order: 64 strided lanes, then a __shfl_down tree); the
+//                        squaring and the first S decimation stages in LDS, with a halo of 10 (2^S - 1) samples; the
+//                        stage-S signal to HBM
 //   levels_tail_kernel   stages S .. Ndec-1 on the stage-S signal, the same way (one value per block)
 //   levels_fir_kernel    the 41-tap FIR and the dB per block, the history ring, and the carried state of the call
 //   levels_scan_kernel   one lane per channel walks the chunks in order: peak hold/decay, the RMS recurrence, both dB
@@ -85,6 +86,10 @@ __device__ inline double load_x(const LvParams& p, int c, long long i) {
     if (p.dtype == 0) return (double)(static_cast<const float*>(p.x))[(size_t)c * p.ld + i];
     return (static_cast<const double*>(p.x))[(size_t)c * p.ld + i];
 }
+
+// np.abs(y).max() (levels.py:97): NaN when either is NaN (fmax would drop it), so that a chunk holding a NaN fails
+// `value_max > old_max (1 - alpha2)` and the peak decays, whatever else the chunk holds
+__device__ inline double nan_max(double m, double a) { return (a > m || a != a) ? a : m; }
 
 // sample j of the carried squared samples followed by this call's input
 __device__ inline double carried_or_input(const LvParams& p, const double* oldc, int c, long long j) {
@@ -168,12 +173,12 @@ __global__ void __launch_bounds__(kThreads) levels_front_kernel(LvParams p) {
         double acc = 0.0, m = 0.0;
         for (long long i = lane; i < len; i += 64) {
             const double v = load_x(p, c, start + i);
-            m = fmax(m, fabs(v));
+            m = nan_max(m, fabs(v));
             if (i < used) acc += (v * v) * kern[i];
         }
         for (int o = 32; o > 0; o >>= 1) {
             acc += __shfl_down(acc, o, 64);
-            m = fmax(m, __shfl_down(m, o, 64));
+            m = nan_max(m, __shfl_down(m, o, 64));
         }
         if (lane == 0) {
             double* d = p.mt + ((size_t)c * p.nchunks + k) * 2;
