@@ -172,6 +172,11 @@ SIGNATURES = {
     "frt_pcmenc_set_stream": (c_int, [c_void_p, c_void_p]),
     "frt_pcmenc_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int,
                                   c_uint64, c_void_p, c_void_p, c_int64]),
+    "frt_loudness_create": (c_int, [POINTER(c_void_p), c_int, c_int, POINTER(c_double), c_int, POINTER(c_double)]),
+    "frt_loudness_destroy": (None, [c_void_p]),
+    "frt_loudness_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_loudness_state_length": (c_int64, [c_void_p, c_int64, c_int64]),
+    "frt_loudness_run": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

@@ -37,7 +37,7 @@ EXTRA_FLAGS = {"iir.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-for
                "specgram.hip": ["-ffp-contract=off"], "levels.hip": ["-ffp-contract=off"], "scope.hip": ["-ffp-contract=off"],
                "curves.hip": ["-ffp-contract=off"], "spectrumbatch.hip": ["-ffp-contract=off"], "specgrambatch.hip": ["-ffp-contract=off"],
                "pitchbatch.hip": ["-ffp-contract=off"], "pitchstream.hip": ["-ffp-contract=off"], "octspecbatch.hip": ["-ffp-contract=off"], "delaybatch.hip": ["-ffp-contract=off"],
-               "delay.hip": ["-ffp-contract=off"], "pcmenc.hip": ["-ffp-contract=off"],
+               "delay.hip": ["-ffp-contract=off"], "pcmenc.hip": ["-ffp-contract=off"], "loudness.hip": ["-ffp-contract=off"],
                "stft.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"]}
 
 

@@ -740,6 +740,60 @@ int frt_pcmenc_encode(frt_pcmenc* h, const void* x, int x_dtype, int n_rows, int
                       const int32_t* route, int channels, int format, int mode, int dither, uint64_t seed, void* dst,
                       int64_t* clipped, int64_t slab_bytes);
 
+/* ---- L2: programme loudness (ITU-R BS.1770-4 / EBU R 128) and true peak (LoudnessBatch) -------------------------------
+ * The reference has no such component; this is the definition.  Samples x[s][k] at 48 kHz, the one rate for which BS.1770
+ * states its coefficients; float64 arithmetic whatever the input dtype (a float32 sample widens exactly).
+ * K-weighting: two biquads in series, each in direct form II transposed in the operation order of lfilter_float64_1D
+ * (y = z0 + b0 x; z0 = (z1 + x b1) - y a1; z1 = x b2 - y a2), no fused multiply-add, zero state at the start of a stream:
+ *   stage 1  b = 1.53512485958697, -2.69169618940638, 1.19839281085285   a = 1, -1.69065929318241, 0.73248077421585
+ *   stage 2  b = 1, -2, 1                                                 a = 1, -1.99004745483398, 0.99007225036621
+ * Sub-blocks of B = 4800 samples (100 ms) on the absolute grid of the stream; only whole sub-blocks have an energy
+ * e[s][b] = sum of y^2.  Its order of additions is fixed by the position in the sub-block: 64 cells of 75 samples, each cell
+ * one ascending chain from 0, the 64 cell sums added in ascending order from 0.  The filter state at the start of cell c of
+ * sub-block b is A^(75 c) s_b + P_c with P_0 = 0, P_(c+1) = A^75 P_c + z_c (z_c: the state after cell c entered with the zero
+ * state) and s_(b+1) = A^4800 s_b + P_64; A^n is the 4x4 matrix whose column j is the state n zero samples after the unit
+ * state e_j, formed by running the biquads; every matrix-vector product is per row (((m0 v0 + m1 v1) + m2 v2) + m3 v3) + z.
+ * This is the sequential recurrence up to rounding (distance measured: DESIGN L2) and the same bits for every grid, stream
+ * count and cut of a recording into calls.
+ * Peaks per sub-block: the sample peak max |x|; the true peak max |u| over the outputs u[m], 4 B b <= m < 4 B (b + 1), that
+ * exist (m < 4 N for a flushed stream of N samples), u being R1's output for L = 4, M = 1, C = 4 tp_zeros and the given
+ * prototype (R1's definition as it stands: one ascending fma chain per output, x = 0 outside the stream; K = 2 tp_zeros + 1).
+ * A stream that is not flushed has emitted max(0, floor((N - tp_zeros) / B)) sub-blocks after N samples (the last true-peak tap
+ * of a sub-block arrives tp_zeros samples past its end); a flushed one has floor(N / B) energies and ceil(N / B) peak entries
+ * (a partial last sub-block has peaks and no energy).
+ * Programmes: P = streams / C programmes of C channels with weights G[c] >= 0:
+ *   z400[p][j] = (sum_c G[c] (((e[j] + e[j+1]) + e[j+2]) + e[j+3])) / 19200, channels ascending from 0
+ *   z3s[p][j]  = the same over the 30 sub-blocks from j on, / 144000
+ *   l(z) = -0.691 + 10 log10 z, -inf for z = 0;  momentary = l(z400), short-term = l(z3s)
+ * Integrated: over the blocks with l(z400) > -70, Gamma = l(their mean) - 10; the result is l(mean of the z400 with l > -70
+ * and l > Gamma) over EVERY block of the stream so far, -inf when none passes the absolute gate.  (Loudness range, EBU Tech
+ * 3342, is a sort of the short-term series: friture_amd/loudness.py.)
+ * The state after n_in samples and E sub-blocks with an energy is one array of doubles,
+ *   filter states [S][4] at the start of sub-block E | samples E B - tp_zeros .. n_in - 1 [S][n_in - E B + tp_zeros] (zeros
+ *   before the stream) | the last min(29, E) energies [S][..] | z400 [P][max(0, E - 3)] | z3s [P][max(0, E - 29)]
+ * of frt_loudness_state_length(h, n_in, E) entries, and the results of a call that takes the stream from (first_in, E) to
+ * (first_in + n, E') with K' peak entries are another,
+ *   energy [S][E' - E] | true peak [S][K' - E] | sample peak [S][K' - E] | momentary [P][new z400] | short-term [P][new z3s] |
+ *   integrated [P]
+ * (linear values; with true_peak = 0 the interpolator is skipped and the true-peak entries are 0). */
+typedef struct frt_loudness frt_loudness;
+/* weights: [channels_per_programme] HOST doubles; prototype: [8 tp_zeros + 1] HOST doubles.  FRT_ERR_INVALID, before any
+ * device call: streams outside 1 .. 65535 or no multiple of channels_per_programme (1 .. 64), a negative or non-finite weight,
+ * tp_zeros outside 1 .. 512, a non-finite prototype. */
+int frt_loudness_create(frt_loudness** h, int streams, int channels_per_programme, const double* weights, int tp_zeros,
+                        const double* prototype);
+void frt_loudness_destroy(frt_loudness* h);
+int frt_loudness_set_stream(frt_loudness* h, void* hip_stream);
+/* pure host: the entries of a state; FRT_ERR_INVALID for a null handle, negative counts or blocks * 4800 > n_in */
+int64_t frt_loudness_state_length(const frt_loudness* h, int64_t n_in, int64_t blocks);
+/* One call over all streams.  x: [streams][ld] float32 (x_dtype 0) or float64 (1), the samples first_in .. first_in + n - 1
+ * (n = 0: x may be NULL).  state_in: the state after first_in samples of a stream that was NOT flushed (NULL: a new stream,
+ * first_in = 0 only); state_out: the state after the call, a buffer distinct from state_in (after flush = 1 it is laid out for
+ * E' = floor(N / B) and is final); out: the results.  Host or device buffers in any mix (host ones are staged); one
+ * synchronisation at the end. */
+int frt_loudness_run(frt_loudness* h, const void* x, int x_dtype, int64_t n, int64_t ld, const double* state_in, double* state_out,
+                     int64_t first_in, int flush, int true_peak, double* out);
+
 #ifdef __cplusplus
 }
 #endif
