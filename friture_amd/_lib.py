@@ -177,6 +177,11 @@ SIGNATURES = {
     "frt_loudness_set_stream": (c_int, [c_void_p, c_void_p]),
     "frt_loudness_state_length": (c_int64, [c_void_p, c_int64, c_int64]),
     "frt_loudness_run": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "frt_transfer_create": (c_int, [POINTER(c_void_p), c_int, c_int64, POINTER(c_double), c_int64, c_int]),
+    "frt_transfer_destroy": (None, [c_void_p]),
+    "frt_transfer_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_transfer_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64,
+                                 c_void_p, POINTER(c_int64)]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

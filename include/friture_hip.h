@@ -794,6 +794,51 @@ int64_t frt_loudness_state_length(const frt_loudness* h, int64_t n_in, int64_t b
 int frt_loudness_run(frt_loudness* h, const void* x, int x_dtype, int64_t n, int64_t ld, const double* state_in, double* state_out,
                      int64_t first_in, int flush, int true_peak, double* out);
 
+/* ---- X1: Welch cross-spectra, transfer function and coherence of two rows (TransferBatch) ----------------------------
+ * The reference has no such component; this is the definition.  A stream is a pair of rows at one sample rate (nothing here
+ * depends on it): x = row 0, the reference, and y = row 1, the measured signal; float64 arithmetic whatever the input dtype
+ * (a float32 sample widens exactly).
+ * Parameters: fft_size N, a power of two in 64 .. 8192; hop >= 1, which may exceed N; a window w of N doubles; average = K >= 1
+ * frames per estimate, or 0 for one running estimate over everything seen; delay d, |d| <= 96000 samples.
+ * Frames: frame f is x[a + f hop .. + N) and y[b + f hop .. + N) with a = max(0, -d), b = max(0, d): a positive delay means
+ * that the measured row lags.  After n samples in total there are F(n) = max(0, floor((n - |d| - N) / hop) + 1) frames.  Per
+ * frame X = rfft(x w) / N and Y = rfft(y w) / N over the bins 0 .. N/2 (with this scale |X|^2 is K1's FRT_STFT_PSD).
+ * Estimates: estimate e is the mean over its frames of |X|^2 (sxx), |Y|^2 (syy) and conj(X) Y (sxy, the convention of
+ * scipy.signal.csd(x, y)).  With average = K it covers the frames e K .. e K + K - 1 and is emitted by the call in which its
+ * last frame completes; a running estimate covers every frame so far and is emitted by every call after which F >= 1.
+ * Derived, written by the device: h1 = sxy / sxx and coherence = |sxy|^2 / (sxx syy); where the denominator is 0 (a silent
+ * row) h1 = 0 and coherence = 0.  Both rows of a frame share one transform, so a row's spectrum is accurate to about 1e-16 of
+ * the LOUDER row's; a row whose windowed frame is all zeros has the spectrum 0 exactly.
+ * Summation order, part of the definition: within an estimate the frames are grouped into runs of RUN = 16 consecutive frames
+ * on the estimate's own frame grid (the last run of an estimate may be short); a run's sum is sequential in frame order from
+ * 0; the run sums are added sequentially in run order from 0, then divided by the frame count.  No atomics: the same bits
+ * for every cut of a recording into calls, every slab size and every batch.
+ * The state after n samples is one array of doubles, S the number of pairs,
+ *   the sum over the complete runs of the open estimate [S][N/2 + 1][4] (sxx, syy, Re sxy, Im sxy) | the sum of the open run
+ *   [S][N/2 + 1][4] | row 0 from min(n, a + F(n) hop) on [S][..] | row 1 from min(n, b + F(n) hop) on [S][..]
+ * (at most N + |d| samples per row), and the results of a call that emits E estimates are another,
+ *   sxy [S][E][N/2 + 1][2] | h1 [S][E][N/2 + 1][2] | sxx [S][E][N/2 + 1] | syy [S][E][N/2 + 1] | coherence [S][E][N/2 + 1]
+ * (complex values as re, im).  Out of scope: N = 16384, fractional delays, exponential averaging. */
+typedef struct frt_transfer frt_transfer;
+/* window: [fft_size] HOST doubles.  FRT_ERR_INVALID, before any device call: fft_size below 64 or no power of two, hop outside
+ * 1 .. 2^30, average < 0, |delay| > 96000, a non-finite window; FRT_ERR_UNSUPPORTED: a power of two above 8192. */
+int frt_transfer_create(frt_transfer** h, int fft_size, int64_t hop, const double* window, int64_t average, int delay);
+void frt_transfer_destroy(frt_transfer* h);
+/* Launches go to the null stream unless another one is set here. */
+int frt_transfer_set_stream(frt_transfer* h, void* hip_stream);
+/* One call over `pairs` streams.  x: float32 (x_dtype 0) or float64 (1); sample t of row r of pair s is x[s pair_stride +
+ * r row_stride + t] (strides in elements, row_stride >= n), the samples first_in .. first_in + n - 1 of the streams (n = 0: x
+ * may be NULL).  state_in: the state after first_in samples (NULL: new streams, first_in = 0 only); state_out: the state
+ * after the call, a buffer distinct from state_in; out: the results (may be NULL when no estimate is emitted);
+ * n_estimates_out (may be NULL): E.  The run partials of one launch stay within scratch_bytes (at least one run per launch):
+ * the frames are cut into time slabs, and the result does not depend on it.  Host or device buffers in any mix (host ones are
+ * staged); one synchronisation at the end.  FRT_ERR_INVALID, before any device call: a null handle, an unknown x_dtype,
+ * pairs outside 1 .. 65535, n < 0, a bad stride, first_in < 0 or first_in + n > 2^40, first_in > 0 without state_in, a null
+ * state_out or one equal to state_in, scratch_bytes < 0, a null out when estimates are emitted. */
+int frt_transfer_run(frt_transfer* h, const void* x, int x_dtype, int pairs, int64_t n, int64_t row_stride, int64_t pair_stride,
+                     const double* state_in, double* state_out, int64_t first_in, int64_t scratch_bytes, double* out,
+                     int64_t* n_estimates_out);
+
 #ifdef __cplusplus
 }
 #endif
