@@ -182,6 +182,13 @@ SIGNATURES = {
     "frt_transfer_set_stream": (c_int, [c_void_p, c_void_p]),
     "frt_transfer_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64,
                                  c_void_p, POINTER(c_int64)]),
+    "frt_convolve_create": (c_int, [POINTER(c_void_p), POINTER(c_double), c_int64, c_int, c_int]),
+    "frt_convolve_destroy": (None, [c_void_p]),
+    "frt_convolve_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_convolve_state_length": (c_int64, [c_void_p, c_int, c_int64]),
+    "frt_convolve_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int64,
+                                 c_void_p, c_int, c_int64, POINTER(c_int64)]),
+    "frt_irfft_rows": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

@@ -38,6 +38,7 @@ EXTRA_FLAGS = {"iir.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-for
                "curves.hip": ["-ffp-contract=off"], "spectrumbatch.hip": ["-ffp-contract=off"], "specgrambatch.hip": ["-ffp-contract=off"],
                "pitchbatch.hip": ["-ffp-contract=off"], "pitchstream.hip": ["-ffp-contract=off"], "octspecbatch.hip": ["-ffp-contract=off"], "delaybatch.hip": ["-ffp-contract=off"],
                "delay.hip": ["-ffp-contract=off"], "pcmenc.hip": ["-ffp-contract=off"], "loudness.hip": ["-ffp-contract=off"],
+               "convolve.hip": ["-ffp-contract=off"],        # X2 fixes its fused multiply-adds itself: every other product rounds on its own
                "stft.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"]}
 
 

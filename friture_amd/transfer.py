@@ -15,8 +15,9 @@ one estimate over all frames so far.  The device also writes h1 = sxy / sxx and 
 the denominator is 0 (a silent row).  The order of the sums is part of the definition: runs of RUN = 16 consecutive frames on
 the estimate's own frame grid (the last may be short), a run summed in frame order, the run sums added in run order, then the
 division by the frame count; no atomics, so a recording cut into calls anywhere, any slab size and any batch give the same
-bits.  Out of scope: N = 16384, fractional delays, exponential averaging, impulse responses, more than two rows per stream,
-resampling (to_48k first).  There is no CPU fallback: run() goes to the HIP library."""
+bits.  Out of scope: N = 16384, fractional delays, exponential averaging, more than two rows per stream, resampling (to_48k
+first).  The impulse response behind h1 and its use on a signal: convolve.impulse_response, convolve.ConvolveBatch (X2).  There
+is no CPU fallback: run() goes to the HIP library."""
 from __future__ import annotations
 
 import ctypes

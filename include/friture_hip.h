@@ -818,7 +818,8 @@ int frt_loudness_run(frt_loudness* h, const void* x, int x_dtype, int64_t n, int
  *   [S][N/2 + 1][4] | row 0 from min(n, a + F(n) hop) on [S][..] | row 1 from min(n, b + F(n) hop) on [S][..]
  * (at most N + |d| samples per row), and the results of a call that emits E estimates are another,
  *   sxy [S][E][N/2 + 1][2] | h1 [S][E][N/2 + 1][2] | sxx [S][E][N/2 + 1] | syy [S][E][N/2 + 1] | coherence [S][E][N/2 + 1]
- * (complex values as re, im).  Out of scope: N = 16384, fractional delays, exponential averaging. */
+ * (complex values as re, im).  Out of scope: N = 16384, fractional delays, exponential averaging.  The impulse response
+ * behind an h1 and its use on a signal: X2. */
 typedef struct frt_transfer frt_transfer;
 /* window: [fft_size] HOST doubles.  FRT_ERR_INVALID, before any device call: fft_size below 64 or no power of two, hop outside
  * 1 .. 2^30, average < 0, |delay| > 96000, a non-finite window; FRT_ERR_UNSUPPORTED: a power of two above 8192. */
@@ -838,6 +839,60 @@ int frt_transfer_set_stream(frt_transfer* h, void* hip_stream);
 int frt_transfer_run(frt_transfer* h, const void* x, int x_dtype, int pairs, int64_t n, int64_t row_stride, int64_t pair_stride,
                      const double* state_in, double* state_out, int64_t first_in, int64_t scratch_bytes, double* out,
                      int64_t* n_estimates_out);
+
+/* ---- X2: uniformly partitioned FFT convolution of rows with a caller's FIR (ConvolveBatch) ----------------------------
+ * The reference has no such component; this is the definition.  A stream is one row x[s][t], t counted from the start of the
+ * stream across calls, x = 0 before it.  The taps h are L doubles, 1 <= L <= 2^18: one filter for all streams, or one per
+ * stream.  The output is y[s][t] = sum_{l < L} h[s][l] x[s][t - l]; float64 arithmetic whatever the input dtype (a float32
+ * sample widens exactly), and a float32 output is one rounding of the float64 value.
+ * Block size: B, a power of two in 64 .. 4096; by default the smallest power of two >= L, clamped to 64 .. 4096.
+ * P = ceil(L / B) <= 4096 partitions; H_p = the real 2 B-point transform of h[p B .. p B + B) followed by B zeros, bins
+ * 0 .. B.  X_w = the real 2 B-point transform of the window x[(w - 1) B .. (w + 1) B) (overlap-save).
+ * Output blocks: block j is y[j B .. j B + B), on the grid of absolute sample indices, which depends on nothing but B.  It is
+ * the last B samples of the inverse real 2 B-point transform of Y_j = sum_{p = 0 .. P - 1} X_{j - p} H_p.
+ * Order of the arithmetic, part of the definition: a real 2 B-point transform is one B-point complex transform of
+ * z[n] = x[2 n] + i x[2 n + 1] and the unpack X[k] = Ze[k] + w^k Zo[k], Ze = (Z[k] + conj Z[B - k]) / 2, Zo = -i (Z[k] - conj
+ * Z[B - k]) / 2, w = exp(-i pi / B); Y_j[k] starts at 0 and takes the terms p = 0, 1, .. in order, each as four fused
+ * multiply-adds (re += Xr Hr; re -= Xi Hi; im += Xr Hi; im += Xi Hr); the inverse is the pack Z[k] = ((A + B') + i conj(w^k)
+ * (A - B')) / (2 B), A = Y[k], B' = conj Y[B - k], and one B-point complex transform.  No atomics.
+ * Bit identity: a block's bits depend on its whole window, so a call that does not flush emits complete blocks only: after n
+ * samples in total a stream has emitted floor(n / B) B outputs.  A flushed stream continues with zeros and has emitted
+ * n + L - 1 outputs; after a flush the state is final (none is written).  A recording cut into calls at any sample, any
+ * scratch_bytes, and a stream alone or in a batch give the same bits as one whole call.
+ * The state after n samples is the input samples max(0, (floor(n / B) - P) B) .. n - 1 as doubles [S][..] (at most
+ * (P + 1) B - 1 per stream: frt_convolve_state_length); n itself travels beside it (first_in).
+ * Out of scope: fractional or time-varying filters, non-uniform partitions, a low-latency live object, a direct time-domain
+ * path for short L, deconvolution by spectral division. */
+typedef struct frt_convolve frt_convolve;
+/* taps: [filters][L] HOST doubles; block: 0 for the default.  The tap spectra H [filters][P][B + 1] are made once, on the
+ * device.  FRT_ERR_INVALID, before any device call: a null handle pointer or null taps, L outside 1 .. 2^18, filters outside
+ * 1 .. 65535, a block that is neither 0 nor a power of two in 64 .. 4096, P > 4096, non-finite taps; FRT_ERR_UNSUPPORTED: H
+ * would exceed 1 GiB. */
+int frt_convolve_create(frt_convolve** h, const double* taps, int64_t L, int filters, int block);
+void frt_convolve_destroy(frt_convolve* h);
+/* Launches go to the null stream unless another one is set here. */
+int frt_convolve_set_stream(frt_convolve* h, void* hip_stream);
+/* pure host: the doubles of the state of `streams` streams after n_in samples; negative for a null handle or bad counts */
+int64_t frt_convolve_state_length(const frt_convolve* h, int streams, int64_t n_in);
+/* One call over `streams` rows.  x: float32 (x_dtype 0) or float64 (1), sample t of row s is x[s row_stride + t] (stride in
+ * elements, >= n), the samples first_in .. first_in + n - 1 of the streams (n = 0: x may be NULL).  state_in: the state
+ * after first_in samples of streams that were not flushed (NULL: new streams, first_in = 0 only); state_out: the state after
+ * the call, a buffer distinct from state_in (flush = 1: not written, may be NULL).  y: float32 (y_dtype 0) or float64 (1),
+ * y[s y_stride + i] is output floor(first_in / B) B + i; *n_out (may be NULL): the outputs per row, floor((first_in + n) / B) B
+ * - floor(first_in / B) B, or with flush = 1 first_in + n + L - 1 - floor(first_in / B) B.  The window spectra of one launch
+ * stay within scratch_bytes (at least one block per launch): the blocks are cut into time slabs, each transforming the P - 1
+ * windows before its first block again, and the result does not depend on it.  Host or device buffers in any mix (host ones
+ * are staged); one synchronisation at the end.  FRT_ERR_INVALID, before any device call: a null handle, an unknown dtype,
+ * streams outside 1 .. 65535, a handle of neither 1 nor `streams` filters, n < 0, a bad stride, first_in < 0 or first_in + n
+ * > 2^40, first_in > 0 without state_in, a null state_out when samples are carried or one equal to state_in, scratch_bytes < 0,
+ * a null y when outputs are emitted. */
+int frt_convolve_run(frt_convolve* h, const void* x, int x_dtype, int streams, int64_t n, int64_t row_stride, const double* state_in,
+                     double* state_out, int64_t first_in, int flush, int64_t scratch_bytes, void* y, int y_dtype, int64_t y_stride,
+                     int64_t* n_out);
+/* out[r] = the inverse real n-point transform of the half spectrum spec[r] (bins 0 .. n/2 as re, im; the imaginary parts of
+ * bins 0 and n/2 do not count), scaled by 1 / n as numpy.fft.irfft: the impulse response behind X1's h1.  n: a power of two
+ * in 64 .. 8192.  Host or device buffers in any mix; launched on hip_stream (NULL: the null stream), synchronised. */
+int frt_irfft_rows(const double* spec, int64_t rows, int n, double* out, void* hip_stream);
 
 #ifdef __cplusplus
 }
