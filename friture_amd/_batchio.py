@@ -1,9 +1,11 @@
-"""What the batch classes (LevelsBatch, ScopeBatch, CurveBatch, SpectrumBatch, SpectrogramBatch, PitchBatch, OctaveSpectrumBatch,
-DelayEstimatorBatch) share: their input is a float32/float64 numpy array or CUDA tensor, their results are of the same kind, and a
-recording is seen in chunks (chunk_ends, checked_ends, frame_schedule); for the five chains over recordings, the host side of
-run(): the input checks (check_keep, check_samples; `dual` for the delay estimator's two rows per stream), the hand-over to the
-null stream, the device copy of a carried state (carried) and the way back to numpy (to_host); for the two STFT chains, the sample
-front (RecordingFront)."""
+"""What the batch classes share.  All of them (LevelsBatch, ScopeBatch, CurveBatch, SpectrumBatch, SpectrogramBatch, PitchBatch,
+OctaveSpectrumBatch, DelayEstimatorBatch, Resampler, LoudnessBatch, TransferBatch, ConvolveBatch): their input is a float32/float64
+numpy array or CUDA tensor and their results are of the same kind (ptr, source, alloc).  The widget batches: a recording is seen
+in chunks (chunk_ends, checked_ends, frame_schedule); for the five chains over recordings, the host side of run(): the input
+checks (check_keep, check_samples; `dual` for two rows per stream), the hand-over to the null stream, the device copy of a
+carried state (carried) and the way back to numpy (to_host); for the two STFT chains, the sample front (RecordingFront).  The
+recording chains (Resampler, LoudnessBatch, TransferBatch, ConvolveBatch): the checks of the stream count and of scratch_bytes,
+the rows read in place (strided_rows) and the numpy / CUDA fork of run() (run_call)."""
 from __future__ import annotations
 
 import ctypes
@@ -107,6 +109,31 @@ def check_samples(who, x, state, dual=False):
     return x, is_np, squeeze, 0 if state is None else int(state.pending)
 
 
+def check_streams(S):
+    if not 1 <= S <= 65535:
+        raise ValueError(f"expected 1 .. 65535 streams, got {S}")
+
+
+def check_scratch_bytes(scratch_bytes):
+    if isinstance(scratch_bytes, bool) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
+        raise ValueError(f"scratch_bytes must be an integer >= 0, got {scratch_bytes!r}")
+
+
+def strided_rows(x, dual=False):
+    """(x, address, dtype code, row stride, pair stride) of the rows x [S, T] ([S, 2, T] with `dual`) of a recording chain, strides
+    in elements: read in place where source(x, strided=True) can, from a contiguous copy when the rows overlap (a broadcast
+    view).  The row stride is at least max(T, 1), whatever a single row's own says; the pair stride is 0 without `dual` and for
+    S = 1."""
+    S, T = x.shape[0], x.shape[-1]
+    for strided in (True, False):
+        x, address, code, strides = source(x, strided)
+        row = strides[-2] if dual or S > 1 else T
+        pair = strides[0] if dual and S > 1 else 0
+        if not T or (row >= T and pair >= 0):
+            break
+    return x, address, code, max(row, T, 1), pair
+
+
 @contextmanager
 def null_stream(x, is_np):
     """The batch kernels launch on the null stream (friture_hip.h): inside, everything is enqueued there, after whatever the
@@ -131,6 +158,27 @@ def carried(dev, value, shape, fill=0.0, copy=True):
         return torch.full(shape, fill, dtype=torch.float64, device=dev) if fill else torch.zeros(shape, dtype=torch.float64, device=dev)
     value = torch.as_tensor(value).to(device=dev, dtype=torch.float64).reshape(shape)
     return value.clone() if copy else value.contiguous()
+
+
+def run_call(x, is_np, outputs, set_stream, call, state, device_state=None):
+    """The numpy / CUDA fork of a recording chain's run(): call(state_in, *outputs()) and the outputs.  outputs() makes the new
+    arrays of x's kind.  numpy: the carried `state` goes in as a host float64 array (None: a fresh stream).  CUDA: everything
+    happens inside null_stream, the outputs are made there, set_stream() points the handle at the null stream, and the state
+    goes in as device_state(dev, state); default: None for a fresh stream, otherwise the state as it is when it is a
+    contiguous float64 tensor on dev (it is only read)."""
+    if is_np:
+        outs = outputs()
+        call(None if state is None else np.ascontiguousarray(to_host(state), np.float64), *outs)
+        return outs
+    with null_stream(x, is_np) as dev:
+        outs = outputs()
+        set_stream()
+        if device_state is not None:
+            state = device_state(dev, state)
+        elif state is not None:
+            state = carried(dev, state, tuple(state.shape), copy=False)
+        call(state, *outs)
+    return outs
 
 
 def to_host(value):

@@ -250,6 +250,25 @@ def init(device: int | None = None) -> ctypes.CDLL:
     return lib
 
 
+class Handle:
+    """One frt_<kind> object of the initialised library `lib`, owned: `h`, a c_void_p made by frt_<kind>_create(&h, *args) and
+    released by frt_<kind>_destroy when the Handle goes."""
+
+    def __init__(self, kind, *args):
+        self.lib, self.kind = init(), kind
+        self.h = c_void_p()
+        check(getattr(self.lib, f"frt_{kind}_create")(ctypes.byref(self.h), *args))
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h.value:
+            getattr(self.lib, f"frt_{self.kind}_destroy")(self.h)
+            self.h = c_void_p()
+
+    def set_stream(self, stream=None):
+        """The stream of the next calls (None: the null stream)."""
+        check(getattr(self.lib, f"frt_{self.kind}_set_stream")(self.h, stream))
+
+
 def set_option(name: str, value: int) -> None:
     """frt_set_option: force one of two product code paths of an entry point (tests, A/B runs); value < 0 restores the
     shape rule.  The library never reads the environment."""

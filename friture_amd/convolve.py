@@ -120,18 +120,16 @@ class ConvolveBatch:
     # ---- device ---------------------------------------------------------------------------------------------------------------
     def _handle(self):
         if self._handle_ is None:
-            self._handle_ = _Handle(self)
+            self._handle_ = _lib.Handle("convolve", self.taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), self.L, self.filters, self.block)
         return self._handle_
 
     def run(self, x, state=None, flush=True, dtype=None, scratch_bytes=1 << 28):
         x, is_np, squeeze, _ = _batchio.check_samples("ConvolveBatch", x, None)
         S, T = x.shape
-        if not 1 <= S <= 65535:
-            raise ValueError(f"expected 1 .. 65535 streams, got {S}")
+        _batchio.check_streams(S)
         if self.per_stream and self.filters != S:
             raise ValueError(f"{self.filters} filters for {S} streams")
-        if isinstance(scratch_bytes, bool) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
-            raise ValueError(f"scratch_bytes must be an integer >= 0, got {scratch_bytes!r}")
+        _batchio.check_scratch_bytes(scratch_bytes)
         out_name = _dtype_name(dtype) if dtype is not None else str(x.dtype).split(".")[-1]
         tail, n_in = self._check_state(state, S)
         flush = bool(flush)
@@ -139,46 +137,21 @@ class ConvolveBatch:
         n_out = self.emitted_after(N, flush) - self.emitted_after(n_in)
         n_tail = 0 if flush else self.state_length(N)
         h = self._handle()
-        x, xptr, code, strides = _batchio.source(x, strided=True)
-        row = strides[0] if S > 1 else T
-        if T and row < T:                                            # rows that overlap (a broadcast view)
-            x, xptr, code, strides = _batchio.source(x, strided=False)
-            row = strides[0] if S > 1 else T
+        x, xptr, code, row, _ = _batchio.strided_rows(x)
         vp = ctypes.c_void_p
         got = ctypes.c_int64(0)
 
         def call(state_in, state_out, y):
-            _lib.check(h.lib.frt_convolve_run(h.h, vp(xptr) if T else None, code, S, T, max(row, T), vp(_batchio.ptr(state_in)),
+            _lib.check(h.lib.frt_convolve_run(h.h, vp(xptr) if T else None, code, S, T, row, vp(_batchio.ptr(state_in)),
                                               vp(_batchio.ptr(state_out)), n_in, int(flush), int(scratch_bytes),
                                               vp(_batchio.ptr(y)) if n_out else None, int(out_name == "float64"), n_out, ctypes.byref(got)))
 
-        if is_np:
-            new = None if flush else _batchio.alloc(x, (S, n_tail))
-            y = _batchio.alloc(x, (S, n_out), out_name)
-            call(None if tail is None else np.ascontiguousarray(_batchio.to_host(tail), np.float64), new, y)
-        else:
-            with _batchio.null_stream(x, is_np) as dev:
-                new = None if flush else _batchio.alloc(x, (S, n_tail))
-                y = _batchio.alloc(x, (S, n_out), out_name)
-                _lib.check(h.lib.frt_convolve_set_stream(h.h, None))
-                call(None if tail is None else _batchio.carried(dev, tail, tuple(tail.shape), copy=False), new, y)
+        def outputs():                                               # a flushed stream has no state
+            return None if flush else _batchio.alloc(x, (S, n_tail)), _batchio.alloc(x, (S, n_out), out_name)
+
+        new, y = _batchio.run_call(x, is_np, outputs, h.set_stream, call, tail)
         assert got.value == n_out
         return ConvolveResult(y[0] if squeeze else y, ConvolveState(new, S, N, self.emitted_after(N, flush), self.settings))
-
-
-class _Handle:
-    """One frt_convolve object: the tap spectra and the twiddle tables on the device."""
-
-    def __init__(self, b):
-        self.lib = _lib.init()
-        self.h = ctypes.c_void_p()
-        _lib.check(self.lib.frt_convolve_create(ctypes.byref(self.h), b.taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), b.L, b.filters,
-                                                b.block))
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.frt_convolve_destroy(self.h)
-            self.h = ctypes.c_void_p()
 
 
 def convolve(x, h, block=None):

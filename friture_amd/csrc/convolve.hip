@@ -23,7 +23,8 @@
 #include <vector>
 
 #include "common.h"
-#include "fft_core.h"
+#include "hostio.h"
+#include "rfft64.h"
 
 using namespace frt;
 
@@ -34,16 +35,8 @@ constexpr long long kMaxTaps = 1LL << 18, kMaxPartitions = 4096, kMaxSamples = 1
 constexpr long long kMaxTableBytes = 1LL << 30;
 constexpr long long kMaxWindows = 1LL << 24;      // windows per launch (the grid's x extent)
 
-using C = cpx<double>;
-
-template <int LOG2B>
-struct Plan {
-    static constexpr int B = 1 << LOG2B, TPF = B / 8;
-    static constexpr bool WAVE_LOCAL = TPF <= 64;
-    static constexpr int BLOCK = WAVE_LOCAL ? 64 : TPF;
-    static constexpr int IPB = BLOCK / TPF;                     // frame groups per workgroup
-    static constexpr size_t LDS = (size_t)IPB * lds_padded_size(B) * sizeof(C);
-};
+using rfft64::C;
+using rfft64::Plan;                               // Plan<LOG2B>: N = B, IPB frame groups per workgroup
 
 // where the samples of a row are: positions t0 .. first_in - 1 in the carried tail, first_in .. end - 1 in the call's rows,
 // zeros elsewhere
@@ -74,7 +67,7 @@ struct WindowParams {
 template <int LOG2B>
 __global__ __launch_bounds__(Plan<LOG2B>::BLOCK) void cv_window_kernel(const WindowParams p) {
     using R = Plan<LOG2B>;
-    constexpr int B = R::B, TPF = R::TPF;
+    constexpr int B = R::N, TPF = R::TPF;
     constexpr bool WL = R::WAVE_LOCAL;
     extern __shared__ __attribute__((aligned(16))) char cv_smem[];
     const int tid = threadIdx.x, item = tid / TPF, i = tid - item * TPF;
@@ -130,7 +123,7 @@ __global__ __launch_bounds__(Plan<LOG2B>::BLOCK) void cv_window_kernel(const Win
 template <int LOG2B>
 __device__ __forceinline__ void inverse_real(C (&y)[8], C ynyq, C* buf, int i, const C* tw, const C* tw2) {
     using R = Plan<LOG2B>;
-    constexpr int B = R::B, TPF = R::TPF;
+    constexpr int B = R::N, TPF = R::TPF;
     constexpr bool WL = R::WAVE_LOCAL;
     const double scale = 0.5 / (double)B;                        // a power of two: exact wherever it is applied
     pass_sync<WL>();                                             // whoever used buf before is done with it
@@ -174,7 +167,7 @@ __device__ __forceinline__ void cfma(C& acc, C x, C h) {
 template <int LOG2B>
 __global__ __launch_bounds__(Plan<LOG2B>::BLOCK) void cv_block_kernel(const BlockParams p) {
     using R = Plan<LOG2B>;
-    constexpr int B = R::B, TPF = R::TPF, J = kTile;
+    constexpr int B = R::N, TPF = R::TPF, J = kTile;
     extern __shared__ __attribute__((aligned(16))) char cv_smem[];
     const int tid = threadIdx.x, item = tid / TPF, i = tid - item * TPF;
     C* buf = reinterpret_cast<C*>(cv_smem) + item * lds_padded_size(B);
@@ -280,7 +273,7 @@ struct IrfftParams {
 template <int LOG2B>
 __global__ __launch_bounds__(Plan<LOG2B>::BLOCK) void cv_irfft_kernel(const IrfftParams p) {
     using R = Plan<LOG2B>;
-    constexpr int B = R::B, TPF = R::TPF;
+    constexpr int B = R::N, TPF = R::TPF;
     extern __shared__ __attribute__((aligned(16))) char cv_smem[];
     const int tid = threadIdx.x, item = tid / TPF, i = tid - item * TPF;
     C* buf = reinterpret_cast<C*>(cv_smem) + item * lds_padded_size(B);
@@ -310,81 +303,14 @@ typedef void (*WindowKernel)(const WindowParams);
 typedef void (*BlockKernel)(const BlockParams);
 typedef void (*IrfftKernel)(const IrfftParams);
 
-struct Instance {
-    WindowKernel window;
-    BlockKernel block;
-    int threads, ipb;
-    size_t lds;
-};
-
-template <int LOG2B>
-Instance instance() {
-    using R = Plan<LOG2B>;
-    return Instance{cv_window_kernel<LOG2B>, cv_block_kernel<LOG2B>, R::BLOCK, R::IPB, R::LDS};
-}
-
-bool instance_for(int log2b, Instance& out) {
-    switch (log2b) {
-        case 6: out = instance<6>(); return true;
-        case 7: out = instance<7>(); return true;
-        case 8: out = instance<8>(); return true;
-        case 9: out = instance<9>(); return true;
-        case 10: out = instance<10>(); return true;
-        case 11: out = instance<11>(); return true;
-        case 12: out = instance<12>(); return true;
-    }
-    return false;
-}
-
-struct IrfftInstance {
-    IrfftKernel kernel;
-    int threads, ipb;
-    size_t lds;
-};
-
-template <int LOG2B>
-IrfftInstance irfft_instance() {
-    using R = Plan<LOG2B>;
-    return IrfftInstance{cv_irfft_kernel<LOG2B>, R::BLOCK, R::IPB, R::LDS};
-}
-
-bool irfft_instance_for(int log2b, IrfftInstance& out) {
-    switch (log2b) {
-        case 5: out = irfft_instance<5>(); return true;
-        case 6: out = irfft_instance<6>(); return true;
-        case 7: out = irfft_instance<7>(); return true;
-        case 8: out = irfft_instance<8>(); return true;
-        case 9: out = irfft_instance<9>(); return true;
-        case 10: out = irfft_instance<10>(); return true;
-        case 11: out = irfft_instance<11>(); return true;
-        case 12: out = irfft_instance<12>(); return true;
-    }
-    return false;
-}
-
-// tw[n] = exp(-2 pi i n / B) and tw2[n] = exp(-i pi n / B), n < B, as one host vector [2 B]
-std::vector<C> twiddles(int B) {
-    std::vector<C> t((size_t)2 * B);
-    const long double step = -3.14159265358979323846264338327950288L / (long double)B;
-    for (int n = 0; n < B; ++n) {
-        t[n] = C{(double)cosl(2.0L * step * n), (double)sinl(2.0L * step * n)};
-        t[B + n] = C{(double)cosl(step * n), (double)sinl(step * n)};
-    }
-    return t;
-}
-
-int log2_of(long long v) {
-    int l = 0;
-    while ((1LL << l) < v) ++l;
-    return l;
-}
-
 }  // namespace
 
 struct frt_convolve {
     int B = 0, P = 0, filters = 0;
     long long L = 0;
-    Instance inst{};
+    WindowKernel window = nullptr;
+    BlockKernel block = nullptr;
+    rfft64::Launch launch{};
     hipStream_t stream = nullptr;
     DeviceBuffer H, tw, xin, sin, sout, yout, spec;
 };
@@ -394,8 +320,8 @@ namespace {
 long long tail_start(const frt_convolve* h, long long n) { return std::max(0LL, (n / h->B - h->P) * (long long)h->B); }
 
 int launch_windows(const frt_convolve* h, const WindowParams& p, int S, hipStream_t stream) {
-    const unsigned blocks = (unsigned)((p.nw + h->inst.ipb - 1) / h->inst.ipb);
-    hipLaunchKernelGGL(h->inst.window, dim3(blocks, S), dim3(h->inst.threads), h->inst.lds, stream, p);
+    const unsigned blocks = (unsigned)((p.nw + h->launch.ipb - 1) / h->launch.ipb);
+    hipLaunchKernelGGL(h->window, dim3(blocks, S), dim3(h->launch.block), h->launch.lds, stream, p);
     FRT_HIP_CHECK(hipGetLastError());
     return FRT_OK;
 }
@@ -411,7 +337,7 @@ extern "C" int frt_convolve_create(frt_convolve** out, const double* taps, int64
     FRT_REQUIRE(block == 0 || (block >= 64 && block <= 4096 && (block & (block - 1)) == 0),
                 "frt_convolve_create: block %d (0: the default, or a power of two in 64 .. 4096)", block);
     int B = block;
-    if (!B) B = (int)std::min<long long>(4096, std::max<long long>(64, 1LL << log2_of(L)));
+    if (!B) B = (int)std::min<long long>(4096, std::max<long long>(64, 1LL << rfft64::log2_of(L)));
     const long long P = (L + B - 1) / B;
     FRT_REQUIRE(P <= kMaxPartitions, "frt_convolve_create: %lld partitions of block %d for L %lld (at most 4096)", P, B, (long long)L);
     const long long table = (long long)filters * P * (B + 1) * (long long)sizeof(C);
@@ -426,20 +352,21 @@ extern "C" int frt_convolve_create(frt_convolve** out, const double* taps, int64
     h->P = (int)P;
     h->L = L;
     h->filters = filters;
-    if (!instance_for(log2_of(B), h->inst)) {
+    const bool found = rfft64::dispatch<6, 12>(rfft64::log2_of(B), [&](auto log2b) {
+        h->window = cv_window_kernel<decltype(log2b)::value>;
+        h->block = cv_block_kernel<decltype(log2b)::value>;
+        h->launch = rfft64::launch_of<decltype(log2b)::value>();
+    });
+    if (!found) {
         delete h;
         set_last_error("frt_convolve_create: no kernel for block %d", B);
         return FRT_ERR_UNSUPPORTED;
     }
-    int rc = upload(h->tw, twiddles(B));
+    int rc = upload(h->tw, rfft64::twiddles(B, true));
     if (!rc) rc = h->H.reserve((size_t)table);
     if (!rc) rc = h->xin.reserve((size_t)filters * L * sizeof(double));
-    for (const void* k : {(const void*)h->inst.window, (const void*)h->inst.block}) {
-        if (!rc && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->inst.lds) != hipSuccess) {
-            set_last_error("frt_convolve_create: %zu bytes of LDS per workgroup refused for block %d", h->inst.lds, B);
-            rc = FRT_ERR_HIP;
-        }
-    }
+    for (const void* k : {(const void*)h->window, (const void*)h->block})
+        if (!rc) rc = rfft64::allow_lds(k, h->launch.lds, "frt_convolve_create", "block", B);
     if (!rc) {
         // H_p: the transform of h[p B .. p B + B), zeros behind it, by the kernel that transforms the streams' windows
         WindowParams p{};
@@ -521,38 +448,17 @@ extern "C" int frt_convolve_run(frt_convolve* h, const void* x, int x_dtype, int
     const size_t xsize = x_dtype ? sizeof(double) : sizeof(float), ysize = y_dtype ? sizeof(double) : sizeof(float);
     int rc;
     Source src{x, x_dtype, row_stride, n0, n1, nullptr, t0, lt};          // behind n1: zeros (a flushed stream reads them)
-    if (n > 0 && !is_device_pointer(x)) {
-        if ((rc = h->xin.reserve((size_t)S * n * xsize))) return rc;
-        FRT_HIP_CHECK(hipMemcpy2DAsync(h->xin.ptr, n * xsize, x, (S == 1 ? n : row_stride) * xsize, n * xsize, (size_t)S, hipMemcpyHostToDevice,
-                                       h->stream));
-        src.x = h->xin.ptr;
-        src.row_stride = n;
-    }
+    HostIO io(h->stream);
+    if ((rc = io.in_rows(h->xin, src.x, src.row_stride, S, n, xsize))) return rc;
     if (state_in && lt > 0) {
         src.tail = state_in;
-        if (!is_device_pointer(state_in)) {
-            if ((rc = h->sin.reserve((size_t)S * lt * sizeof(double)))) return rc;
-            FRT_HIP_CHECK(hipMemcpyAsync(h->sin.ptr, state_in, (size_t)S * lt * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            src.tail = h->sin.as<const double>();
-        }
+        if ((rc = io.in(h->sin, src.tail, (size_t)S * lt))) return rc;
     } else {
         src.t0 = n0;                                             // nothing carried
         src.lt = 0;
     }
-    const bool y_dev = !y || is_device_pointer(y);
-    void* dy = y;
-    long long dy_stride = y_stride;
-    if (!y_dev && n_out > 0) {
-        if ((rc = h->yout.reserve((size_t)S * n_out * ysize))) return rc;
-        dy = h->yout.ptr;
-        dy_stride = n_out;
-    }
-    const bool s_dev = !state_out || is_device_pointer(state_out);
-    double* dso = state_out;
-    if (!s_dev && nlt > 0) {
-        if ((rc = h->sout.reserve((size_t)S * nlt * sizeof(double)))) return rc;
-        dso = h->sout.as<double>();
-    }
+    if ((rc = io.out(h->sout, state_out, (size_t)S * nlt))) return rc;
+    if ((rc = io.out_rows(h->yout, y, y_stride, S, n_out, ysize))) return rc;
 
     // time slabs: the spectra of one launch (the windows of its blocks and the P - 1 before them, transformed again) stay
     // within scratch_bytes, at least one block per launch
@@ -581,28 +487,23 @@ extern "C" int frt_convolve_run(frt_convolve* h, const void* x, int x_dtype, int
         k.P = P;
         k.ja = a;
         k.jb = b;
-        k.y = dy;
+        k.y = y;
         k.y_dtype = y_dtype;
-        k.y_stride = dy_stride;
+        k.y_stride = y_stride;
         k.out_begin = out_begin;
         k.out_end = out_end;
         k.tw = w.tw;
         k.tw2 = w.tw2;
         const long long tiles = (b - a + kTile - 1) / kTile;
-        hipLaunchKernelGGL(h->inst.block, dim3((unsigned)((tiles + h->inst.ipb - 1) / h->inst.ipb), S), dim3(h->inst.threads), h->inst.lds,
+        hipLaunchKernelGGL(h->block, dim3((unsigned)((tiles + h->launch.ipb - 1) / h->launch.ipb), S), dim3(h->launch.block), h->launch.lds,
                            h->stream, k);
         FRT_HIP_CHECK(hipGetLastError());
     }
     if (nlt > 0) {
-        hipLaunchKernelGGL(cv_tail_kernel, dim3((unsigned)((nlt + 255) / 256), S), dim3(256), 0, h->stream, src, dso, nt0, nlt);
+        hipLaunchKernelGGL(cv_tail_kernel, dim3((unsigned)((nlt + 255) / 256), S), dim3(256), 0, h->stream, src, state_out, nt0, nlt);
         FRT_HIP_CHECK(hipGetLastError());
-        if (!s_dev) FRT_HIP_CHECK(hipMemcpyAsync(state_out, dso, (size_t)S * nlt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
-    if (!y_dev && n_out > 0)
-        FRT_HIP_CHECK(hipMemcpy2DAsync(y, (S == 1 ? n_out : y_stride) * ysize, dy, n_out * ysize, n_out * ysize, (size_t)S, hipMemcpyDeviceToHost,
-                                       h->stream));
-    FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return FRT_OK;
+    return io.finish();
 }
 
 extern "C" int frt_irfft_rows(const double* spec, int64_t rows, int n, double* out, void* hip_stream) {
@@ -611,8 +512,13 @@ extern "C" int frt_irfft_rows(const double* spec, int64_t rows, int n, double* o
     FRT_REQUIRE(rows == 0 || (spec && out), "frt_irfft_rows: null buffer");
     if (rows == 0) return FRT_OK;
     const int B = n / 2;
-    IrfftInstance inst{};
-    if (!irfft_instance_for(log2_of(B), inst)) {
+    IrfftKernel kernel = nullptr;
+    rfft64::Launch launch{};
+    const bool found = rfft64::dispatch<5, 12>(rfft64::log2_of(B), [&](auto log2b) {
+        kernel = cv_irfft_kernel<decltype(log2b)::value>;
+        launch = rfft64::launch_of<decltype(log2b)::value>();
+    });
+    if (!found) {
         set_last_error("frt_irfft_rows: no kernel for n %d", n);
         return FRT_ERR_UNSUPPORTED;
     }
@@ -624,7 +530,7 @@ extern "C" int frt_irfft_rows(const double* spec, int64_t rows, int n, double* o
     int rc = work.reserve(tw_bytes + (in_dev ? 0 : in_bytes) + (out_dev ? 0 : out_bytes));
     if (rc) return rc;
     auto run = [&]() -> int {
-        const std::vector<C> tw = twiddles(B);
+        const std::vector<C> tw = rfft64::twiddles(B, true);
         FRT_HIP_CHECK(hipMemcpyAsync(work.ptr, tw.data(), tw_bytes, hipMemcpyHostToDevice, stream));
         FRT_HIP_CHECK(hipStreamSynchronize(stream));             // tw leaves scope; pageable copies are staged, this keeps it plain
         char* at = work.as<char>() + tw_bytes;
@@ -639,11 +545,9 @@ extern "C" int frt_irfft_rows(const double* spec, int64_t rows, int n, double* o
         p.rows = rows;
         p.tw = work.as<const C>();
         p.tw2 = p.tw + B;
-        if (hipFuncSetAttribute((const void*)inst.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)inst.lds) != hipSuccess) {
-            set_last_error("frt_irfft_rows: %zu bytes of LDS per workgroup refused for n %d", inst.lds, n);
-            return FRT_ERR_HIP;
-        }
-        hipLaunchKernelGGL(inst.kernel, dim3((unsigned)((rows + inst.ipb - 1) / inst.ipb)), dim3(inst.threads), inst.lds, stream, p);
+        int r = rfft64::allow_lds((const void*)kernel, launch.lds, "frt_irfft_rows", "n", n);
+        if (r) return r;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + launch.ipb - 1) / launch.ipb)), dim3(launch.block), launch.lds, stream, p);
         FRT_HIP_CHECK(hipGetLastError());
         if (!out_dev) FRT_HIP_CHECK(hipMemcpyAsync(out, p.out, out_bytes, hipMemcpyDeviceToHost, stream));
         FRT_HIP_CHECK(hipStreamSynchronize(stream));

@@ -27,6 +27,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "hostio.h"
 
 namespace frt {
 namespace {
@@ -603,25 +604,16 @@ extern "C" int frt_levels_run(frt_levels* h, const void* x, int dtype, int64_t n
     const long long nb = long_out ? (h->r - kHist + n) >> h->ndec : 0;
     if (nblocks) *nblocks = nb;
     const size_t esize = dtype ? sizeof(double) : sizeof(float);
-    const void* xd = x;
+    const size_t mcount = meters_out ? (size_t)h->C * nchunks * kFields : 0, lcount = long_out ? (size_t)h->C * nb * 2 : 0;
+    HostIO io(h->stream);
     int rc;
-    if (n > 0 && !is_device_pointer(x)) {
-        if ((rc = h->xin.reserve((size_t)h->C * n * esize))) return rc;
-        FRT_HIP_CHECK(hipMemcpy2DAsync(h->xin.ptr, n * esize, x, ld * esize, n * esize, h->C, hipMemcpyHostToDevice, h->stream));
-        xd = h->xin.ptr;
-        ld = n;
-    }
-    const size_t mbytes = meters_out ? (size_t)h->C * nchunks * kFields * sizeof(double) : 0;
-    const size_t lbytes = long_out ? (size_t)h->C * nb * 2 * sizeof(double) : 0;
-    const bool m_dev = meters_out && is_device_pointer(meters_out), l_dev = long_out && is_device_pointer(long_out);
-    if ((rc = h->outs.reserve(std::max<size_t>(mbytes + lbytes, 64)))) return rc;
-    double* dm = meters_out ? (m_dev ? meters_out : h->outs.as<double>()) : nullptr;
-    double* dl = long_out ? (l_dev ? long_out : h->outs.as<double>() + mbytes / sizeof(double)) : nullptr;
-    if ((rc = run_device(h, xd, dtype, n, ld, h->C, chunk, nchunks, dm, dl, false, nullptr))) return rc;
-    if (meters_out && !m_dev && mbytes) FRT_HIP_CHECK(hipMemcpyAsync(meters_out, dm, mbytes, hipMemcpyDeviceToHost, h->stream));
-    if (long_out && !l_dev && lbytes) FRT_HIP_CHECK(hipMemcpyAsync(long_out, dl, lbytes, hipMemcpyDeviceToHost, h->stream));
-    FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return FRT_OK;
+    if ((rc = io.in_rows(h->xin, x, ld, h->C, n, esize))) return rc;
+    // one block for both outputs; a host output has its twin in it even when it has no elements: null means "not asked for"
+    if ((rc = h->outs.reserve(std::max<size_t>((mcount + lcount) * sizeof(double), 64)))) return rc;
+    if ((rc = io.out_at(meters_out, h->outs.as<double>(), mcount))) return rc;
+    if ((rc = io.out_at(long_out, h->outs.as<double>() + mcount, lcount))) return rc;
+    if ((rc = run_device(h, x, dtype, n, ld, h->C, chunk, nchunks, meters_out, long_out, false, nullptr))) return rc;
+    return io.finish();
 }
 
 extern "C" int frt_levels_push(frt_levels* h, const double* x_host, int nch, int64_t n, double* meters_out, double* long_out,
@@ -677,37 +669,23 @@ extern "C" int frt_levels_subsample(frt_levels* h, const void* x, int dtype, int
     if (n == 0) return FRT_OK;                                          // longlevels.py:74-75: an empty push returns it
     FRT_REQUIRE(x && out, "frt_levels_subsample: null buffer");
     const size_t esize = dtype ? sizeof(double) : sizeof(float);
-    const void* xd = x;
+    HostIO io(h->stream);
     int rc;
-    if (!is_device_pointer(x)) {
-        if ((rc = h->xin.reserve((size_t)h->C * n * esize))) return rc;
-        FRT_HIP_CHECK(hipMemcpy2DAsync(h->xin.ptr, n * esize, x, ld * esize, n * esize, h->C, hipMemcpyHostToDevice, h->stream));
-        xd = h->xin.ptr;
-        ld = n;
-    }
-    const bool o_dev = is_device_pointer(out);
-    const size_t obytes = (size_t)h->C * m * sizeof(double);
-    if (!o_dev && (rc = h->outs.reserve(obytes))) return rc;
-    double* dout = o_dev ? out : h->outs.as<double>();
-    if ((rc = run_device(h, xd, dtype, n, ld, h->C, 1, 0, nullptr, dout, true, nullptr))) return rc;
-    if (!o_dev) FRT_HIP_CHECK(hipMemcpyAsync(out, dout, obytes, hipMemcpyDeviceToHost, h->stream));
-    FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return FRT_OK;
+    if ((rc = io.in_rows(h->xin, x, ld, h->C, n, esize))) return rc;
+    if ((rc = io.out(h->outs, out, (size_t)h->C * m))) return rc;
+    if ((rc = run_device(h, x, dtype, n, ld, h->C, 1, 0, nullptr, out, true, nullptr))) return rc;
+    return io.finish();
 }
 
 extern "C" int frt_levels_history(frt_levels* h, int64_t count, double* out) {
     FRT_REQUIRE(h && out, "frt_levels_history: null argument");
     FRT_REQUIRE(count >= 0 && count <= h->H, "frt_levels_history: %lld entries of a ring of %lld", (long long)count, h->H);
     if (count == 0) return FRT_OK;
-    const bool o_dev = is_device_pointer(out);
-    const size_t bytes = (size_t)h->C * count * sizeof(double);
+    HostIO io(h->stream);
     int rc;
-    if (!o_dev && (rc = h->hist.reserve(bytes))) return rc;
-    double* d = o_dev ? out : h->hist.as<double>();
+    if ((rc = io.out(h->hist, out, (size_t)h->C * count))) return rc;
     hipLaunchKernelGGL(levels_history_kernel, dim3((unsigned)((count + 255) / 256), h->C), dim3(256), 0, h->stream, h->ring.as<const double>(),
-                       h->H, h->ring_total, (long long)count, h->C, d);
+                       h->H, h->ring_total, (long long)count, h->C, out);
     FRT_HIP_CHECK(hipGetLastError());
-    if (!o_dev) FRT_HIP_CHECK(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream));
-    FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return FRT_OK;
+    return io.finish();
 }

@@ -22,6 +22,7 @@
 // This translation unit is compiled with -ffp-contract=off: the biquads are the operation order of the definition, and the only
 // fused multiply-adds are the fma() calls of the interpolator, which are part of ITS definition (R1).
 #include "common.h"
+#include "hostio.h"
 
 #include <algorithm>
 #include <cmath>
@@ -531,29 +532,13 @@ extern "C" int frt_loudness_run(frt_loudness* h, const void* x, int x_dtype, int
     p.x = x;
     p.n = n;
     p.ld = ld;
-    if (n > 0 && !is_device_pointer(x)) {
-        if ((rc = h->xin.reserve((size_t)S * n * esize))) return rc;
-        FRT_HIP_CHECK(hipMemcpy2DAsync(h->xin.ptr, n * esize, x, ld * esize, n * esize, S, hipMemcpyHostToDevice, h->stream));
-        p.x = h->xin.ptr;
-        p.ld = n;
-    }
+    HostIO io(h->stream);
+    if ((rc = io.in_rows(h->xin, p.x, p.ld, S, n, esize))) return rc;
     const double* din = state_in;
-    if (state_in && !is_device_pointer(state_in)) {
-        if ((rc = h->sin.reserve(in_len * sizeof(double)))) return rc;
-        FRT_HIP_CHECK(hipMemcpyAsync(h->sin.ptr, state_in, in_len * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        din = h->sin.as<const double>();
-    }
-    const bool s_dev = is_device_pointer(state_out), o_dev = is_device_pointer(out);
-    double* dso = state_out;
-    if (!s_dev) {
-        if ((rc = h->sout.reserve(out_state_len * sizeof(double)))) return rc;
-        dso = h->sout.as<double>();
-    }
-    double* dout = out;
-    if (!o_dev) {
-        if ((rc = h->out.reserve(out_len * sizeof(double)))) return rc;
-        dout = h->out.as<double>();
-    }
+    if ((rc = io.in(h->sin, din, in_len))) return rc;
+    double *dso = state_out, *dout = out;
+    if ((rc = io.out(h->sout, dso, out_state_len))) return rc;
+    if ((rc = io.out(h->out, dout, out_len))) return rc;
     if (ne > 0) {
         if ((rc = h->pref.reserve((size_t)S * ne * kCells * 4 * sizeof(double)))) return rc;
         if ((rc = h->zb.reserve((size_t)S * ne * 4 * sizeof(double)))) return rc;
@@ -613,8 +598,5 @@ extern "C" int frt_loudness_run(frt_loudness* h, const void* x, int x_dtype, int
     if ((rc = x_dtype ? launch<double>(h, p, r, filt_out, samples_out, e1 * kB - R, len_out, tail_out, tl_out)
                       : launch<float>(h, p, r, filt_out, samples_out, e1 * kB - R, len_out, tail_out, tl_out)))
         return rc;
-    if (!s_dev) FRT_HIP_CHECK(hipMemcpyAsync(state_out, dso, out_state_len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (!o_dev) FRT_HIP_CHECK(hipMemcpyAsync(out, dout, out_len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return FRT_OK;
+    return io.finish();
 }

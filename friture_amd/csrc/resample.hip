@@ -12,6 +12,7 @@
 // the period and by nothing else (not the tile, the grid, the stream count or where a call was cut).  L = 1 and M = 1 are the
 // same code with one column, or with kb advancing by less than a sample per output.
 #include "common.h"
+#include "hostio.h"
 
 #include <algorithm>
 #include <numeric>
@@ -228,7 +229,7 @@ extern "C" int frt_resample_run(frt_resample* h, const void* x, int x_dtype, int
     FRT_REQUIRE(!tail_out || tail_out != tail_in, "frt_resample_run: the tail cannot be updated in place");
     const int Kt = h->K - 1;
     const size_t esize = x_dtype ? sizeof(double) : sizeof(float), osize = y_dtype ? sizeof(double) : sizeof(float);
-    const size_t tbytes = (size_t)h->S * Kt * sizeof(double);
+    const size_t tcount = (size_t)h->S * Kt;
     Params p{};
     p.x = x;
     p.tail = tail_in;
@@ -248,29 +249,12 @@ extern "C" int frt_resample_run(frt_resample* h, const void* x, int x_dtype, int
     p.span = h->span;
     p.copy = (h->span + 2) / 2 * 2;
     p.direct = h->direct;
+    HostIO io(h->stream);
     int rc;
-    if (n > 0 && !is_device_pointer(x)) {
-        if ((rc = h->xin.reserve((size_t)h->S * n * esize))) return rc;
-        FRT_HIP_CHECK(hipMemcpy2DAsync(h->xin.ptr, n * esize, x, ld * esize, n * esize, h->S, hipMemcpyHostToDevice, h->stream));
-        p.x = h->xin.ptr;
-        p.ld = n;
-    }
-    if (tail_in && !is_device_pointer(tail_in)) {
-        if ((rc = h->tin.reserve(tbytes))) return rc;
-        FRT_HIP_CHECK(hipMemcpyAsync(h->tin.ptr, tail_in, tbytes, hipMemcpyHostToDevice, h->stream));
-        p.tail = h->tin.as<const double>();
-    }
-    const bool t_dev = tail_out && is_device_pointer(tail_out), y_dev = n_out > 0 && is_device_pointer(y);
-    double* dt = tail_out;
-    if (tail_out && !t_dev) {
-        if ((rc = h->tout.reserve(tbytes))) return rc;
-        dt = h->tout.as<double>();
-    }
-    if (n_out > 0 && !y_dev) {
-        if ((rc = h->yout.reserve((size_t)h->S * n_out * osize))) return rc;
-        p.y = h->yout.ptr;
-        p.ldy = n_out;
-    }
+    if ((rc = io.in_rows(h->xin, p.x, p.ld, h->S, n, esize))) return rc;
+    if ((rc = io.in(h->tin, p.tail, tcount))) return rc;
+    if ((rc = io.out(h->tout, tail_out, tcount))) return rc;
+    if ((rc = io.out_rows(h->yout, p.y, p.ldy, h->S, n_out, osize))) return rc;
     long long tiles = 0;
     if (n_out > 0) {
         p.Pbase = first_out / h->L;
@@ -278,10 +262,6 @@ extern "C" int frt_resample_run(frt_resample* h, const void* x, int x_dtype, int
         tiles = (periods + kPeriods * h->np - 1) / (kPeriods * h->np);
         FRT_REQUIRE(tiles <= 0x7fffffffLL, "frt_resample_run: %lld outputs in one call", (long long)n_out);
     }
-    if ((rc = x_dtype ? launch<double>(h, p, y_dtype, (unsigned)tiles, dt) : launch<float>(h, p, y_dtype, (unsigned)tiles, dt))) return rc;
-    if (tail_out && !t_dev) FRT_HIP_CHECK(hipMemcpyAsync(tail_out, dt, tbytes, hipMemcpyDeviceToHost, h->stream));
-    if (n_out > 0 && !y_dev)
-        FRT_HIP_CHECK(hipMemcpy2DAsync(y, ldy * osize, p.y, n_out * osize, n_out * osize, h->S, hipMemcpyDeviceToHost, h->stream));
-    FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return FRT_OK;
+    if ((rc = x_dtype ? launch<double>(h, p, y_dtype, (unsigned)tiles, tail_out) : launch<float>(h, p, y_dtype, (unsigned)tiles, tail_out))) return rc;
+    return io.finish();
 }

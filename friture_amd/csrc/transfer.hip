@@ -20,7 +20,8 @@
 #include <vector>
 
 #include "common.h"
-#include "fft_core.h"
+#include "hostio.h"
+#include "rfft64.h"
 
 using namespace frt;
 
@@ -71,15 +72,6 @@ __device__ __forceinline__ double sample_at(const Params& p, long long row, cons
     return p.dtype ? reinterpret_cast<const double*>(p.x)[at] : (double)reinterpret_cast<const float*>(p.x)[at];
 }
 
-template <int LOG2N>
-struct RunPlan {
-    static constexpr int N = 1 << LOG2N, TPF = N / 8, BINS = N / 2 + 1;
-    static constexpr bool WAVE_LOCAL = TPF <= 64;
-    static constexpr int BLOCK = WAVE_LOCAL ? 64 : TPF;
-    static constexpr int IPB = BLOCK / TPF;                     // runs per workgroup
-    static constexpr size_t LDS = (size_t)IPB * lds_padded_size(N) * sizeof(cpx<double>);
-};
-
 struct alignas(16) Sum4 {            // one bin of a partial or a state block: sxx, syy, Re sxy, Im sxy
     double x, y, z, w;
 };
@@ -103,10 +95,10 @@ struct Sums {
 };
 
 template <int LOG2N>
-__global__ __launch_bounds__(RunPlan<LOG2N>::BLOCK) void tf_run_kernel(const Params p) {
-    using R = RunPlan<LOG2N>;
+__global__ __launch_bounds__(rfft64::Plan<LOG2N>::BLOCK) void tf_run_kernel(const Params p) {
+    using R = rfft64::Plan<LOG2N>;                               // R::IPB runs per workgroup
     using C = cpx<double>;
-    constexpr int N = R::N, TPF = R::TPF, BINS = R::BINS;
+    constexpr int N = R::N, TPF = R::TPF, BINS = N / 2 + 1;
     constexpr bool WL = R::WAVE_LOCAL;
     extern __shared__ __attribute__((aligned(16))) char tf_smem[];
     const int tid = threadIdx.x, item = tid / TPF, i = tid - item * TPF;
@@ -306,38 +298,13 @@ __global__ void tf_tail_kernel(const Params p, double* out_x, long long nx0, lon
 
 typedef void (*RunKernel)(const Params);
 
-struct Instance {
-    RunKernel kernel;
-    int block, ipb;
-    size_t lds;
-};
-
-template <int LOG2N>
-Instance instance() {
-    using R = RunPlan<LOG2N>;
-    return Instance{tf_run_kernel<LOG2N>, R::BLOCK, R::IPB, R::LDS};
-}
-
-bool instance_for(int log2n, Instance& out) {
-    switch (log2n) {
-        case 6: out = instance<6>(); return true;
-        case 7: out = instance<7>(); return true;
-        case 8: out = instance<8>(); return true;
-        case 9: out = instance<9>(); return true;
-        case 10: out = instance<10>(); return true;
-        case 11: out = instance<11>(); return true;
-        case 12: out = instance<12>(); return true;
-        case 13: out = instance<13>(); return true;
-    }
-    return false;
-}
-
 }  // namespace
 
 struct frt_transfer {
     int N = 0, bins = 0, d = 0;
     long long hop = 0, K = 0, rpe = 0, a = 0, b = 0;
-    Instance inst{};
+    RunKernel kernel = nullptr;
+    rfft64::Launch launch{};
     hipStream_t stream = nullptr;
     DeviceBuffer window, tw, xin, sin, sout, out, part, sums[2];
 };
@@ -365,8 +332,6 @@ extern "C" int frt_transfer_create(frt_transfer** out, int fft_size, int64_t hop
     FRT_REQUIRE(delay >= -kMaxDelay && delay <= kMaxDelay, "frt_transfer_create: delay %d (-%d .. %d samples)", delay, kMaxDelay, kMaxDelay);
     FRT_REQUIRE(window && !is_device_pointer(window), "frt_transfer_create: the window is a host array of %d doubles", fft_size);
     for (int i = 0; i < fft_size; ++i) FRT_REQUIRE(std::isfinite(window[i]), "frt_transfer_create: window[%d] is not finite", i);
-    int log2n = 0;
-    while ((1 << log2n) < fft_size) ++log2n;
     frt_transfer* h = new frt_transfer();
     h->N = fft_size;
     h->bins = fft_size / 2 + 1;
@@ -376,21 +341,19 @@ extern "C" int frt_transfer_create(frt_transfer** out, int fft_size, int64_t hop
     h->rpe = (h->K + kRun - 1) / kRun;
     h->a = delay < 0 ? -delay : 0;
     h->b = delay > 0 ? delay : 0;
-    if (!instance_for(log2n, h->inst)) {
+    const bool found = rfft64::dispatch<6, 13>(rfft64::log2_of(fft_size), [&](auto log2n) {
+        h->kernel = tf_run_kernel<decltype(log2n)::value>;
+        h->launch = rfft64::launch_of<decltype(log2n)::value>();
+    });
+    if (!found) {
         delete h;
         set_last_error("frt_transfer_create: no kernel for fft_size %d", fft_size);
         return FRT_ERR_UNSUPPORTED;
     }
     std::vector<double> w(window, window + fft_size);
-    std::vector<cpx<double>> tw((size_t)fft_size);
-    const long double step = -2.0L * 3.14159265358979323846264338327950288L / (long double)fft_size;
-    for (int n = 0; n < fft_size; ++n) tw[n] = cpx<double>{(double)cosl(step * n), (double)sinl(step * n)};
     int rc = upload(h->window, w);
-    if (!rc) rc = upload(h->tw, tw);
-    if (!rc && hipFuncSetAttribute((const void*)h->inst.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->inst.lds) != hipSuccess) {
-        set_last_error("frt_transfer_create: %zu bytes of LDS per workgroup refused for fft_size %d", h->inst.lds, fft_size);
-        rc = FRT_ERR_HIP;
-    }
+    if (!rc) rc = upload(h->tw, rfft64::twiddles(fft_size, false));
+    if (!rc) rc = rfft64::allow_lds((const void*)h->kernel, h->launch.lds, "frt_transfer_create", "fft_size", fft_size);
     if (rc) {
         frt_transfer_destroy(h);
         return rc;
@@ -448,37 +411,13 @@ extern "C" int frt_transfer_run(frt_transfer* h, const void* x, int x_dtype, int
     p.dtype = x_dtype;
     p.row_stride = row_stride;
     p.pair_stride = pair_stride;
-    if (n > 0 && !is_device_pointer(x)) {
-        if ((rc = h->xin.reserve((size_t)S * 2 * n * esize))) return rc;
-        const char* src = reinterpret_cast<const char*>(x);
-        if (S == 1 || pair_stride == 2 * row_stride) {
-            FRT_HIP_CHECK(hipMemcpy2DAsync(h->xin.ptr, n * esize, src, row_stride * esize, n * esize, 2 * (size_t)S, hipMemcpyHostToDevice, h->stream));
-        } else {
-            for (int s = 0; s < S; ++s)
-                FRT_HIP_CHECK(hipMemcpy2DAsync(h->xin.as<char>() + (size_t)s * 2 * n * esize, n * esize, src + (size_t)s * pair_stride * esize,
-                                               row_stride * esize, n * esize, 2, hipMemcpyHostToDevice, h->stream));
-        }
-        p.x = h->xin.ptr;
-        p.row_stride = n;
-        p.pair_stride = 2 * n;
-    }
+    HostIO io(h->stream);
+    if ((rc = io.in_rows(h->xin, p.x, p.row_stride, p.pair_stride, S, 2, n, esize))) return rc;      // pairs of rows; as one copy when evenly spaced
     const double* din = state_in;
-    if (state_in && !is_device_pointer(state_in)) {
-        if ((rc = h->sin.reserve(in_len * sizeof(double)))) return rc;
-        FRT_HIP_CHECK(hipMemcpyAsync(h->sin.ptr, state_in, in_len * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        din = h->sin.as<const double>();
-    }
-    const bool s_dev = is_device_pointer(state_out), o_dev = !out || is_device_pointer(out);
-    double* dso = state_out;
-    if (!s_dev) {
-        if ((rc = h->sout.reserve(out_state_len * sizeof(double)))) return rc;
-        dso = h->sout.as<double>();
-    }
-    double* dout = out;
-    if (!o_dev) {
-        if ((rc = h->out.reserve(out_len * sizeof(double)))) return rc;
-        dout = h->out.as<double>();
-    }
+    if ((rc = io.in(h->sin, din, in_len))) return rc;
+    double *dso = state_out, *dout = out;
+    if ((rc = io.out(h->sout, dso, out_state_len))) return rc;
+    if ((rc = io.out(h->out, dout, out_len))) return rc;
     // the state: estimate sums [S][bins][4] | open run [S][bins][4] | row 0 from tx0 [S][lx] | row 1 from ty0 [S][ly]
     p.first_in = n0;
     p.tail_x = din ? din + 2 * head : nullptr;
@@ -530,8 +469,8 @@ extern "C" int frt_transfer_run(frt_transfer* h, const void* x, int x_dtype, int
         if (nruns > 0) {
             if ((rc = h->part.reserve((size_t)nruns * run_bytes))) return rc;
             p.part = h->part.as<double>();
-            const unsigned blocks = (unsigned)((nruns + h->inst.ipb - 1) / h->inst.ipb);
-            hipLaunchKernelGGL(h->inst.kernel, dim3(blocks, S), dim3(h->inst.block), h->inst.lds, h->stream, p);
+            const unsigned blocks = (unsigned)((nruns + h->launch.ipb - 1) / h->launch.ipb);
+            hipLaunchKernelGGL(h->kernel, dim3(blocks, S), dim3(h->launch.block), h->launch.lds, h->stream, p);
             FRT_HIP_CHECK(hipGetLastError());
         }
         Finish f{};
@@ -569,8 +508,5 @@ extern "C" int frt_transfer_run(frt_transfer* h, const void* x, int x_dtype, int
                            out_x + (size_t)S * nlx, ny0, nly);
         FRT_HIP_CHECK(hipGetLastError());
     }
-    if (!s_dev) FRT_HIP_CHECK(hipMemcpyAsync(state_out, dso, out_state_len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (!o_dev && out_len) FRT_HIP_CHECK(hipMemcpyAsync(out, dout, out_len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    FRT_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return FRT_OK;
+    return io.finish();
 }

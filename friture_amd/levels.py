@@ -43,28 +43,19 @@ def ndec_for(response_time):
     return int(max(0, np.floor((np.log2(response_time * SAMPLING_RATE/100.)))))
 
 
-class _Handle:
+class _Handle(_lib.Handle):
     """One frt_levels object: channels, Ndec, ring of history_len entries."""
 
     def __init__(self, channels, ndec, history_len, kernel=None, alpha=0.0, alpha2=0.0):
         from .longlevels import gauss
-        lib = _lib.init()
         if kernel is None:
             kernel = np.zeros(1)
         self._kernel = np.ascontiguousarray(kernel, np.float64)
         g11 = np.ascontiguousarray(gauss(11, 2.), np.float64)
         g41 = np.ascontiguousarray(gauss(10*4+1, 2.*4), np.float64)
         self.channels = channels
-        self.h = ctypes.c_void_p()
-        _lib.check(lib.frt_levels_create(ctypes.byref(self.h), channels, ndec, int(history_len), self._kernel.ctypes.data_as(_DP),
-                                         self._kernel.shape[0], float(alpha), float(alpha2), g11.ctypes.data_as(_DP),
-                                         g41.ctypes.data_as(_DP), PEAK_DECAY_RATE))
-        self.lib = lib
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.frt_levels_destroy(self.h)
-            self.h = ctypes.c_void_p()
+        super().__init__("levels", channels, ndec, int(history_len), self._kernel.ctypes.data_as(_DP), self._kernel.shape[0], float(alpha),
+                         float(alpha2), g11.ctypes.data_as(_DP), g41.ctypes.data_as(_DP), PEAK_DECAY_RATE)
 
     def set_ndec(self, ndec):
         _lib.check(self.lib.frt_levels_set_ndec(self.h, int(ndec)))
@@ -160,7 +151,7 @@ class LevelsBatch:
         lo = _batchio.alloc(x, (self.channels, nb, 2)) if long else None
         if not isinstance(x, np.ndarray):
             import torch
-            _lib.check(h.lib.frt_levels_set_stream(h.h, ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+            h.set_stream(ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
         got = ctypes.c_int64(0)
         _lib.check(h.lib.frt_levels_run(h.h, ptr if n else None, dtype, n, n, self.chunk, _batchio.ptr(m), _batchio.ptr(lo),
                                         ctypes.byref(got)))

@@ -207,7 +207,9 @@ class LoudnessBatch:
     # ---- device ---------------------------------------------------------------------------------------------------------------
     def _handle(self, S):
         if S not in self._handles:
-            self._handles[S] = _Handle(self, S)
+            dp = ctypes.POINTER(ctypes.c_double)
+            weights = np.ascontiguousarray(self.weights, np.float64)
+            self._handles[S] = _lib.Handle("loudness", S, self.channels, weights.ctypes.data_as(dp), self.tp_zeros, self.prototype.ctypes.data_as(dp))
         return self._handles[S]
 
     def run(self, x, state=None, flush=True):
@@ -224,25 +226,14 @@ class LoudnessBatch:
                  ("integrated", (P, 1)))
         out_len = sum(a * b for _, (a, b) in parts)
         h = self._handle(S)
-        x, xptr, code, strides = _batchio.source(x, strided=True)
-        ld = strides[0] if S > 1 else max(T, 1)
-        if ld < T:                                                   # rows that overlap (a broadcast view)
-            x, xptr, code, strides = _batchio.source(x, strided=False)
-            ld = max(T, 1)
+        x, xptr, code, ld, _ = _batchio.strided_rows(x)
         vp = ctypes.c_void_p
 
         def call(state_in, state_out, out):
             _lib.check(h.lib.frt_loudness_run(h.h, vp(xptr) if T else None, code, T, ld, vp(_batchio.ptr(state_in)), vp(_batchio.ptr(state_out)),
                                               n_in, int(bool(flush)), int(self.true_peak), vp(_batchio.ptr(out))))
 
-        if is_np:
-            new, out = _batchio.alloc(x, (state_len,)), _batchio.alloc(x, (out_len,))
-            call(None if data is None else np.ascontiguousarray(_batchio.to_host(data), np.float64), new, out)
-        else:
-            with _batchio.null_stream(x, is_np) as dev:
-                new, out = _batchio.alloc(x, (state_len,)), _batchio.alloc(x, (out_len,))
-                _lib.check(h.lib.frt_loudness_set_stream(h.h, None))
-                call(None if data is None else _batchio.carried(dev, data, (data.shape[0],), copy=False), new, out)
+        new, out = _batchio.run_call(x, is_np, lambda: (_batchio.alloc(x, (state_len,)), _batchio.alloc(x, (out_len,))), h.set_stream, call, data)
         res, at = {}, 0
         for name, (a, b) in parts:
             res[name] = out[at:at + a * b].reshape(a, b)
@@ -256,23 +247,6 @@ class LoudnessBatch:
         if squeeze:
             fields = [None if f is None else f[0] for f in fields]
         return LoudnessResult(*fields, LoudnessState(new, S, N, k1))
-
-
-class _Handle:
-    """One frt_loudness object: the interpolator's table, the weights and the cell matrices on the device, for S streams."""
-
-    def __init__(self, b, S):
-        self.lib = _lib.init()
-        self.h = ctypes.c_void_p()
-        dp = ctypes.POINTER(ctypes.c_double)
-        weights = np.ascontiguousarray(b.weights, np.float64)
-        _lib.check(self.lib.frt_loudness_create(ctypes.byref(self.h), S, b.channels, weights.ctypes.data_as(dp), b.tp_zeros,
-                                                b.prototype.ctypes.data_as(dp)))
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.frt_loudness_destroy(self.h)
-            self.h = ctypes.c_void_p()
 
 
 def loudness(x, channels="stereo"):

@@ -135,32 +135,26 @@ def decode_pcm(data, fmt, channels, select=None, start=0, count=None, dtype=np.f
     if is_np and to is None:
         y = np.empty((S, count), name)
         with h.lock:
-            _lib.check(h.lib.frt_pcm_set_stream(h.h, None))
+            h.set_stream()
             call(y)
         return y
     import torch
     with _batchio.null_stream(data, is_np) as dev:
         y = torch.empty((S, count), dtype=getattr(torch, name), device=dev)
         with h.lock:
-            _lib.check(h.lib.frt_pcm_set_stream(h.h, None))
+            h.set_stream()
             call(y)
     return y
 
 
-class _Handle:
-    """One frt_pcm object: the page-locked slabs and the device staging of decode_pcm, kept from call to call and shared by every
-    caller of the process.  A frt_pcm serves one call at a time, so calls from several threads take `lock` in turn."""
+class _Locked(_lib.Handle):
+    """One frt_pcm or frt_pcmenc object: the page-locked slabs and the device staging of decode_pcm or encode_pcm, kept from call
+    to call and shared by every caller of the process.  It serves one call at a time, so calls from several threads take `lock`
+    in turn."""
 
-    def __init__(self):
+    def __init__(self, kind):
         self.lock = threading.Lock()
-        self.lib = _lib.init()
-        self.h = ctypes.c_void_p()
-        _lib.check(self.lib.frt_pcm_create(ctypes.byref(self.h)))
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.frt_pcm_destroy(self.h)
-            self.h = ctypes.c_void_p()
+        super().__init__(kind)
 
 
 _shared = None
@@ -171,7 +165,7 @@ def _handle():
     global _shared
     with _shared_lock:
         if _shared is None:
-            _shared = _Handle()
+            _shared = _Locked("pcm")
         return _shared
 
 
@@ -302,7 +296,7 @@ def encode_pcm(x, fmt, route=None, channels=None, frame0=0, dither=False, seed=0
         if S > 1 and strides[0] < T:                            # rows that overlap (an expanded tensor): read a copy
             src, addr, x_dtype, strides = _batchio.source(x, strided=False)
         with h.lock:
-            _lib.check(h.lib.frt_pcmenc_set_stream(h.h, None))
+            h.set_stream()
             _lib.check(h.lib.frt_pcmenc_encode(h.h, vp(addr) if T else None, x_dtype, S, int(strides[0]) if S > 1 else max(T, 1), T,
                                                frame0, vp(rt.ctypes.data), C, code, MODES[mode], int(dither), seed,
                                                vp(_batchio.ptr(data)) if T else None, vp(clipped.ctypes.data), slab))
@@ -320,21 +314,6 @@ def encode_pcm(x, fmt, route=None, channels=None, frame0=0, dither=False, seed=0
     return EncodedPcm(out, clipped)
 
 
-class _Encoder:
-    """One frt_pcmenc object behind a lock: encode_pcm's page-locked slabs and device staging, as _Handle is decode_pcm's."""
-
-    def __init__(self):
-        self.lock = threading.Lock()
-        self.lib = _lib.init()
-        self.h = ctypes.c_void_p()
-        _lib.check(self.lib.frt_pcmenc_create(ctypes.byref(self.h)))
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.frt_pcmenc_destroy(self.h)
-            self.h = ctypes.c_void_p()
-
-
 _shared_encoder = None
 
 
@@ -342,7 +321,7 @@ def _encoder():
     global _shared_encoder
     with _shared_lock:
         if _shared_encoder is None:
-            _shared_encoder = _Encoder()
+            _shared_encoder = _Locked("pcmenc")
         return _shared_encoder
 
 

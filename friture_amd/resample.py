@@ -97,7 +97,7 @@ class Resampler:
     # ---- device ---------------------------------------------------------------------------------------------------------------
     def _handle(self, S):
         if S not in self._handles:
-            self._handles[S] = _Handle(self, S)
+            self._handles[S] = _lib.Handle("resample", self.L, self.M, self.C, self.prototype.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), S)
         return self._handles[S]
 
     def run(self, x, state=None, flush=True, dtype=None):
@@ -110,39 +110,18 @@ class Resampler:
         total = self.n_out(n_in + T, flush)
         n_new, Kt = total - n_out, self.K - 1
         h = self._handle(S)
-        x, xptr, code, strides = _batchio.source(x, strided=True)
-        ld = strides[0] if S > 1 else max(T, 1)
+        x, xptr, code, ld, _ = _batchio.strided_rows(x)
         vp = ctypes.c_void_p
 
-        def call(tail_in, tail_out, y):
+        def call(tail_in, y, tail_out):
             _lib.check(h.lib.frt_resample_run(h.h, vp(xptr) if T else None, code, T, ld, vp(_batchio.ptr(tail_in)), vp(_batchio.ptr(tail_out)),
                                               n_in, n_out, n_new, vp(_batchio.ptr(y)) if n_new else None,
                                               int(out_name == "float64"), max(n_new, 1)))
 
-        if is_np:
-            y, tail_out = _batchio.alloc(x, (S, n_new), out_name), _batchio.alloc(x, (S, Kt))
-            call(None if tail is None else np.ascontiguousarray(_batchio.to_host(tail), np.float64), tail_out, y)
-        else:
-            with _batchio.null_stream(x, is_np) as dev:
-                y, tail_out = _batchio.alloc(x, (S, n_new), out_name), _batchio.alloc(x, (S, Kt))
-                _lib.check(h.lib.frt_resample_set_stream(h.h, None))
-                call(_batchio.carried(dev, tail, (S, Kt)), tail_out, y)
+        # a fresh stream starts from a zero tail on the device, and a carried one is copied
+        y, tail_out = _batchio.run_call(x, is_np, lambda: (_batchio.alloc(x, (S, n_new), out_name), _batchio.alloc(x, (S, Kt))), h.set_stream,
+                                        call, tail, device_state=lambda dev, tail: _batchio.carried(dev, tail, (S, Kt)))
         return ResampleResult(y[0] if squeeze else y, ResampleState(tail_out, n_in + T, total))
-
-
-class _Handle:
-    """One frt_resample object: the coefficient table of a Resampler on the device, for S streams."""
-
-    def __init__(self, r, S):
-        self.lib = _lib.init()
-        self.h = ctypes.c_void_p()
-        _lib.check(self.lib.frt_resample_create(ctypes.byref(self.h), r.L, r.M, r.C,
-                                                r.prototype.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), S))
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.frt_resample_destroy(self.h)
-            self.h = ctypes.c_void_p()
 
 
 def to_48k(x, rate_in):

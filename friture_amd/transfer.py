@@ -160,46 +160,39 @@ class TransferBatch:
     # ---- device ---------------------------------------------------------------------------------------------------------------
     def _handle(self):
         if self._handle_ is None:
-            self._handle_ = _Handle(self)
+            self._handle_ = _lib.Handle("transfer", self.fft_size, self.hop, self.window.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                        self.average or 0, self.delay)
         return self._handle_
 
     def run(self, x, state=None, scratch_bytes=1 << 28):
         x, is_np, squeeze, _ = _batchio.check_samples("TransferBatch", x, state, dual=True)
         S, T = x.shape[0], x.shape[2]
-        if not 1 <= S <= 65535:
-            raise ValueError(f"expected 1 .. 65535 streams, got {S}")
-        if isinstance(scratch_bytes, bool) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
-            raise ValueError(f"scratch_bytes must be an integer >= 0, got {scratch_bytes!r}")
+        _batchio.check_streams(S)
+        _batchio.check_scratch_bytes(scratch_bytes)
         data, n_in = self._check_state(state, S)
         N = n_in + T
         E, bins = self.emitted(n_in, N), self.bins
         layout, state_len = state_layout(S, self.fft_size, self.hop, self.delay, N)
         h = self._handle()
-        x, xptr, code, strides = _batchio.source(x, strided=True)
-        row, pair = max(strides[1], 1), strides[0] if S > 1 else 0
-        if T and (row < T or pair < 0):                              # rows that overlap (a broadcast view)
-            x, xptr, code, strides = _batchio.source(x, strided=False)
-            row, pair = strides[1], strides[0]
+        x, xptr, code, row, pair = _batchio.strided_rows(x, dual=True)
         vp, seb = ctypes.c_void_p, S * E * bins
         n_est = ctypes.c_int64(0)
 
-        def call(state_in, state_out, out):
-            _lib.check(h.lib.frt_transfer_run(h.h, vp(xptr) if T else None, code, S, T, max(row, T), pair, vp(_batchio.ptr(state_in)),
+        def call(state_in, state_out, out, frames):
+            _lib.check(h.lib.frt_transfer_run(h.h, vp(xptr) if T else None, code, S, T, row, pair, vp(_batchio.ptr(state_in)),
                                               vp(_batchio.ptr(state_out)), n_in, int(scratch_bytes), vp(_batchio.ptr(out)) if seb else None,
                                               ctypes.byref(n_est)))
 
+        def outputs():
+            frames = _batchio.alloc(x, (E,), np.int64)
+            frames[...] = self.average or self.frames_after(N)
+            return _batchio.alloc(x, (state_len,)), _batchio.alloc(x, (7 * seb,)), frames
+
+        new, out, frames = _batchio.run_call(x, is_np, outputs, h.set_stream, call, data)
         if is_np:
-            new, out = _batchio.alloc(x, (state_len,)), _batchio.alloc(x, (7 * seb,))
-            call(None if data is None else np.ascontiguousarray(_batchio.to_host(data), np.float64), new, out)
-            frames = np.full((E,), self.average or self.frames_after(N), np.int64)
             cplx = lambda a: a.view(np.complex128).reshape(S, E, bins)
         else:
             import torch
-            with _batchio.null_stream(x, is_np) as dev:
-                new, out = _batchio.alloc(x, (state_len,)), _batchio.alloc(x, (7 * seb,))
-                _lib.check(h.lib.frt_transfer_set_stream(h.h, None))
-                call(None if data is None else _batchio.carried(dev, data, (data.shape[0],), copy=False), new, out)
-                frames = torch.full((E,), self.average or self.frames_after(N), dtype=torch.int64, device=dev)
             cplx = lambda a: torch.view_as_complex(a.reshape(S, E, bins, 2))
         assert n_est.value == E
         fields = [out[4 * seb:5 * seb].reshape(S, E, bins), out[5 * seb:6 * seb].reshape(S, E, bins), cplx(out[:2 * seb]),
@@ -207,18 +200,3 @@ class TransferBatch:
         if squeeze:
             fields = [f[0] for f in fields]
         return TransferResult(*fields, frames, self.freq, TransferState(new, S, N, layout["row0"][1][1], self.settings))
-
-
-class _Handle:
-    """One frt_transfer object: the window and the twiddle table on the device."""
-
-    def __init__(self, b):
-        self.lib = _lib.init()
-        self.h = ctypes.c_void_p()
-        _lib.check(self.lib.frt_transfer_create(ctypes.byref(self.h), b.fft_size, b.hop, b.window.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                                b.average or 0, b.delay))
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.frt_transfer_destroy(self.h)
-            self.h = ctypes.c_void_p()
