@@ -189,6 +189,12 @@ SIGNATURES = {
     "frt_convolve_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int64,
                                  c_void_p, c_int, c_int64, POINTER(c_int64)]),
     "frt_irfft_rows": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "frt_decay_tile": (c_int, []),
+    "frt_decay_create": (c_int, [POINTER(c_void_p), c_double, c_int, c_double, c_double, c_double]),
+    "frt_decay_destroy": (None, [c_void_p]),
+    "frt_decay_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_decay_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p,
+                              c_void_p, c_void_p]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

@@ -39,6 +39,7 @@ EXTRA_FLAGS = {"iir.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-for
                "pitchbatch.hip": ["-ffp-contract=off"], "pitchstream.hip": ["-ffp-contract=off"], "octspecbatch.hip": ["-ffp-contract=off"], "delaybatch.hip": ["-ffp-contract=off"],
                "delay.hip": ["-ffp-contract=off"], "pcmenc.hip": ["-ffp-contract=off"], "loudness.hip": ["-ffp-contract=off"],
                "convolve.hip": ["-ffp-contract=off"],        # X2 fixes its fused multiply-adds itself: every other product rounds on its own
+               "decay.hip": ["-ffp-contract=off"],           # X3: e[t] is a rounded square, then added
                "stft.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"]}
 
 

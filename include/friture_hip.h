@@ -894,6 +894,66 @@ int frt_convolve_run(frt_convolve* h, const void* x, int x_dtype, int streams, i
  * in 64 .. 8192.  Host or device buffers in any mix; launched on hip_stream (NULL: the null stream), synchronised. */
 int frt_irfft_rows(const double* spec, int64_t rows, int n, double* out, void* hip_stream);
 
+/* ---- X3: reverberation time and clarity from impulse responses (DecayBatch) -----------------------------------------------
+ * The reference has no such component; this is the definition (the ISO 3382 quantities by Schroeder's backward integration).
+ * A row x[0 .. T) is float32 or float64, 1 <= T <= 2^24; fs defaults to 48000.  All arithmetic is float64: e[t] = (double)x[t]^2.
+ * Parameters: block W = 480 samples (any integer in 8 .. 65536), onset_db = -20, noise_tail = 0.1, margin_db = 10.
+ * 1. Peak: p is the smallest t with |x[t]| = max |x|.  A row that is all zero, or that holds a sample that is not finite, is
+ *    a dead row: NaN in every float output, -1 in every index output; it never faults and never affects its neighbours.  (A
+ *    row whose given onset or truncation lies outside its range, which only device arrays can carry this far, is dead too.)
+ * 2. Onset: t0 is the smallest t with |x[t]| >= c |x[p]|, c the double nearest 10^(onset_db / 20), made on the host, the
+ *    product rounded to double: the test is exact.  Or t0 is given per row, 0 <= t0 < T (the bands of one response share
+ *    the broadband onset).
+ * 3. Noise: nb = floor(T / W) blocks, q[k] = the sum of e over [k W, (k + 1) W); nt = max(1, ceil(noise_tail nb));
+ *    N0 = (the sum of the last nt block sums) / (nt W), 0 when nb = 0.
+ * 4. Truncation: auto: t1 = k W for the smallest k > floor(p / W) with q[k] <= W N0 10^(margin_db / 10), T if there is none;
+ *    none: t1 = T; or given per row, t0 < t1 <= T.
+ * 5. Schroeder integral and decay curve, t0 <= t < t1: E[t] = e[t] + .. + e[t1 - 1], L[t] = 10 log10(E[t] / E[t0]).
+ * 6. Decay times over the ranges (hi, lo): EDT (0, -10), T10 (-5, -15), T20 (-5, -25), T30 (-5, -35).  a = the smallest t
+ *    with L[t] <= hi (EDT: a = t0), b = the smallest t with L[t] <= lo; a least-squares line of L[t] over k = t - a, a <= t < b
+ *    (the sums of k and k^2 are closed forms); RT = -60 / (slope fs) seconds, r2 the squared correlation coefficient of the
+ *    same fit; NaN when lo is not reached before t1 or b - a < 2.
+ * 7. Energy ratios, n50 = round(0.05 fs), n80 = round(0.08 fs), E[u] = 0 for u >= t1: C50 = 10 log10((E[t0] - E[t0 + n50]) /
+ *    E[t0 + n50]), C80 the same with n80, D50 = (E[t0] - E[t0 + n50]) / E[t0] (a short response: C = +inf, D50 = 1);
+ *    Ts = sum (t - t0) e[t] / E[t0] / fs over [t0, t1).
+ * 8. level_db = 10 log10 E[t0]; noise_db = 10 log10 N0; dynamic_range = 10 log10(max_k q[k] / (W N0)), NaN when nb = 0 and
+ *    +inf when N0 = 0; the integers peak, onset, truncation.
+ * 9. On request the curve L[t0 + j step], j < ceil(T / step); entries at or behind t1 are NaN.
+ * Order of the sums, per row and anchored at its sample 0 (so the bits of a row depend on no other row, on no slab size, row
+ * stride or input dtype): q[k] by 64 lanes (8 for W < 64), lane i adding e[k W + i], e[k W + i + 64], .. in order, the lanes
+ * folded by a butterfly.  E[t]: tiles of frt_decay_tile() = 512 samples, 8 consecutive samples per lane; E[t] = ((e[t] + ..
+ * + e[last of the lane], added from the back) + a Kogge-Stone scan of the totals of the lanes behind) + the totals of the
+ * tiles behind, added one by one from the row's last tile.  The crossings are counts (a = t0 + the number of t with L[t] >
+ * hi), a sample belongs to the range its own L falls in, and the comparisons are made on E against E[t0] 10^(lo / 10), those
+ * factors made on the host: L is monotone up to the last bit of E, and an input whose crossing hangs on that bit has no
+ * defined index.  The regression sums: per tile lane sums in sample order folded by a butterfly, tile sums 64 apart added
+ * in order and folded by a butterfly.  No atomics.
+ * There is no carried state: a decay is integrated from its end, so a response is given whole.  Out of scope as well:
+ * Lundeby's iteration, the tail-compensation term, noise subtraction, IIR band filters per IEC 61260 class, sample rates
+ * handled in any way other than the fs argument. */
+typedef struct frt_decay frt_decay;
+/* pure host: the tile length of the scan */
+int frt_decay_tile(void);
+/* FRT_ERR_INVALID, before any device call: a null handle pointer, fs outside 100 .. 1e7, block outside 8 .. 65536, onset_db
+ * above 0, noise_tail outside (0, 1], margin_db below 0, anything not finite. */
+int frt_decay_create(frt_decay** h, double fs, int block, double onset_db, double noise_tail, double margin_db);
+void frt_decay_destroy(frt_decay* h);
+/* Launches go to the null stream unless another one is set here. */
+int frt_decay_set_stream(frt_decay* h, void* hip_stream);
+/* One call over `rows` rows of n samples.  x: float32 (x_dtype 0) or float64 (1), sample t of row r is x[r row_stride + t]
+ * (stride in elements, >= n).  onset: [rows] or NULL (step 2 finds it).  truncate_mode 0: t1 = n; 1: auto; 2: truncation
+ * [rows] gives t1.  params [rows][15]: edt, t10, t20, t30 | r2 of the four | c50, c80, d50, ts | level_db, noise_db,
+ * dynamic_range.  indices [rows][3]: peak, onset, truncation.  curve [rows][ceil(n / curve_step)], or NULL with curve_step 0.
+ * The rows are cut into slabs whose scratch stays within scratch_bytes (at least one row per launch); the result does not
+ * depend on it.  Host or device buffers in any mix (host ones are staged); one synchronisation at the end.
+ * FRT_ERR_INVALID, before any launch: a null handle, an unknown x_dtype, rows outside 1 .. 65535, n outside 1 .. 2^24, a null
+ * x, a bad stride, an unknown truncate_mode, truncation without mode 2 or mode 2 without it, curve_step < 0, a curve without
+ * a step or a step without a curve, scratch_bytes < 0, null params or indices, and in host arrays an onset outside 0 .. n - 1
+ * or a truncation outside 1 .. n. */
+int frt_decay_run(frt_decay* h, const void* x, int x_dtype, int rows, int64_t n, int64_t row_stride, const int64_t* onset,
+                  int truncate_mode, const int64_t* truncation, int64_t curve_step, int64_t scratch_bytes, double* params,
+                  int64_t* indices, double* curve);
+
 #ifdef __cplusplus
 }
 #endif
