@@ -195,6 +195,12 @@ SIGNATURES = {
     "frt_decay_set_stream": (c_int, [c_void_p, c_void_p]),
     "frt_decay_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p,
                               c_void_p, c_void_p]),
+    "frt_rfft_long_rows": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "frt_irfft_long_rows": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "frt_deconvolve_create": (c_int, [POINTER(c_void_p), POINTER(c_double), c_int64, c_int, c_int64, c_double, POINTER(c_double)]),
+    "frt_deconvolve_destroy": (None, [c_void_p]),
+    "frt_deconvolve_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_deconvolve_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

@@ -40,6 +40,7 @@ EXTRA_FLAGS = {"iir.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-for
                "delay.hip": ["-ffp-contract=off"], "pcmenc.hip": ["-ffp-contract=off"], "loudness.hip": ["-ffp-contract=off"],
                "convolve.hip": ["-ffp-contract=off"],        # X2 fixes its fused multiply-adds itself: every other product rounds on its own
                "decay.hip": ["-ffp-contract=off"],           # X3: e[t] is a rounded square, then added
+               "deconvolve.hip": ["-ffp-contract=off"],      # X4: every product of the transform and of Y G rounds on its own
                "stft.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"]}
 
 

@@ -13,7 +13,7 @@ depend on its whole window, so a call with flush=False emits complete blocks onl
 total) and returns the state that continues the streams; flush=True continues with zeros, emits up to n + L - 1 and ends the
 streams.  A recording cut into calls at any sample, any scratch_bytes and any batch give the bits of one whole call.  Out of
 scope: fractional or time-varying filters, non-uniform partitions, a low-latency live object, a direct time-domain path for
-short L, deconvolution by spectral division.  There is no CPU fallback: run() goes to the HIP library."""
+short L; deconvolution by spectral division is friture_amd/deconvolve.py.  There is no CPU fallback: run() goes to the HIP library."""
 from __future__ import annotations
 
 import ctypes

@@ -862,7 +862,7 @@ int frt_transfer_run(frt_transfer* h, const void* x, int x_dtype, int pairs, int
  * The state after n samples is the input samples max(0, (floor(n / B) - P) B) .. n - 1 as doubles [S][..] (at most
  * (P + 1) B - 1 per stream: frt_convolve_state_length); n itself travels beside it (first_in).
  * Out of scope: fractional or time-varying filters, non-uniform partitions, a low-latency live object, a direct time-domain
- * path for short L, deconvolution by spectral division. */
+ * path for short L.  Deconvolution by spectral division: X4. */
 typedef struct frt_convolve frt_convolve;
 /* taps: [filters][L] HOST doubles; block: 0 for the default.  The tap spectra H [filters][P][B + 1] are made once, on the
  * device.  FRT_ERR_INVALID, before any device call: a null handle pointer or null taps, L outside 1 .. 2^18, filters outside
@@ -953,6 +953,66 @@ int frt_decay_set_stream(frt_decay* h, void* hip_stream);
 int frt_decay_run(frt_decay* h, const void* x, int x_dtype, int rows, int64_t n, int64_t row_stride, const int64_t* onset,
                   int truncate_mode, const int64_t* truncation, int64_t curve_step, int64_t scratch_bytes, double* params,
                   int64_t* indices, double* curve);
+
+/* ---- X4: long real transforms and deconvolution by spectral division (rfft_rows, irfft_rows, DeconvolveBatch) ---------------
+ * The reference has no such component; this is the definition.  n is a power of two in 2^13 .. 2^24, Mc = n / 2; all
+ * arithmetic is float64 (a float32 sample widens exactly).
+ * 1. Long real transform: X[k] = sum_{t < n} x[t] exp(-2 pi i k t / n), k = 0 .. n/2, as numpy.fft.rfft(x, n); a row of T <= n
+ *    samples (float32 or float64, strided rows read in place) is continued with zeros.  The inverse is numpy.fft.irfft(spec, n):
+ *    the imaginary parts of bins 0 and n/2 do not count, the scale 1 / n is a power of two, and only the first keep <= n
+ *    samples are stored.
+ * 2. Deconvolution: a reference x of 1 <= Lx <= n doubles, one for all rows or one per row.  At creation the device forms
+ *    P[k] = Re X[k]^2 + Im X[k]^2, Pmax = max_k P[k] per reference, and G[k] = conj(X[k]) / (P[k] + r[k] Pmax) (two real
+ *    divisions), 0 where the denominator is 0; r is the scalar reg >= 0 or one value >= 0 per bin (a frequency-dependent,
+ *    Kirkeby-style regularisation).  Per measured row y of T <= n samples: H[k] = Y[k] G[k], one complex product in which every
+ *    multiplication rounds on its own, and h = irfft(H, n)[0 .. keep).  The division is circular: with n >= T the acausal
+ *    part (the harmonic-distortion responses of a sweep) sits at the end of h.  On request H itself is returned.
+ * Order of the arithmetic, part of the definition: the complex transform of z[m] = x[2 m] + i x[2 m + 1] has Mc = N1 N2 points,
+ *    N1 = 2^floor(log2 Mc / 2) <= N2.  With m = n1 N2 + n2 and k = k1 + N1 k2: N1-point transforms over n1 (X1's transform of
+ *    8 points per thread), the product with exp(-2 pi i k1 n2 / Mc), N2-point transforms over n2; then the unpack X[k] = Ze + t,
+ *    X[Mc - k] = conj(Ze - t), t = w^k Zo, Ze = (Z[k] + conj Z[Mc - k]) / 2, Zo = -i (Z[k] - conj Z[Mc - k]) / 2, w = exp(-i pi
+ *    / Mc), for k <= Mc / 2.  The inverse packs W[k] = conj(((A + B) + i conj(w^k) (A - B)) / n), A = H[k], B = conj H[Mc - k],
+ *    runs the same forward transform on W and stores r[2 m] = Re, r[2 m + 1] = -Im.  exp(-2 pi i j / M) between the passes
+ *    (M = Mc) and in the unpack (M = n) is the rounded product of the table entries exp(-2 pi i 4096 floor(j / 4096) / M) and
+ *    exp(-2 pi i (j mod 4096) / M), both made on the host in long double and rounded once.  No atomics, no fused
+ *    multiply-adds.
+ * 3. Bits: a row's bits depend on its own samples, n, the reference and r only: not on the other rows of the call, on
+ *    scratch_bytes, on a row stride, or on host versus device buffers; a float32 row gives the bits of the same values given
+ *    as float64.  A row that holds a non-finite sample gives no finite promise for itself; it never faults and it leaves its
+ *    neighbours' bits alone.
+ * 4. There is no carried state: a division needs the whole spectrum.  Out of scope: n that is no power of two, n < 2^13
+ *    (frt_irfft_rows' range), multi-channel (MIMO) inversion, time-domain windowing of the result, minimum-phase or
+ *    inverse-filter design.
+ * Scratch: two rows of Mc + 1 complex128 per row in flight (256 MB at n = 2^24); the rows are cut into slabs whose scratch
+ * stays within scratch_bytes, at least one row per launch, and the result does not depend on it. */
+/* spec[r] = the bins 0 .. n/2 (re, im) of row r: x float32 (x_dtype 0) or float64 (1), sample t of row r is x[r row_stride + t]
+ * (stride in elements, >= T).  Host or device buffers in any mix; launched on hip_stream (NULL: the null stream), synchronised.
+ * The two stateless entries keep the tables of every n they have served and one grow-only scratch block per process (a block
+ * above 512 MB is released when its call ends); their calls are serialised.
+ * FRT_ERR_INVALID, before any device call: a null buffer, an unknown x_dtype, n no power of two in 2^13 .. 2^24, T outside
+ * 1 .. n, rows outside 1 .. 65535, a bad stride, scratch_bytes < 0. */
+int frt_rfft_long_rows(const void* x, int x_dtype, int rows, int64_t T, int64_t row_stride, int64_t n, int64_t scratch_bytes,
+                       double* spec, void* hip_stream);
+/* out[r out_stride + t], t < keep = the inverse real n-point transform of spec[r] ([rows][n/2 + 1] as re, im).  Buffers,
+ * stream and errors as above; keep outside 1 .. n is FRT_ERR_INVALID. */
+int frt_irfft_long_rows(const double* spec, int rows, int64_t n, int64_t keep, int64_t scratch_bytes, double* out, int64_t out_stride,
+                        void* hip_stream);
+typedef struct frt_deconvolve frt_deconvolve;
+/* x: [refs][Lx] HOST doubles; reg_bins: NULL (reg holds for every bin) or [n/2 + 1] HOST doubles that replace reg.  G
+ * [refs][n/2 + 1] is made once, on the device.  FRT_ERR_INVALID, before any device call: a null handle pointer or null x, n no
+ * power of two in 2^13 .. 2^24, Lx outside 1 .. n, refs outside 1 .. 65535, a negative or non-finite reg or reg_bins value, a
+ * non-finite reference; FRT_ERR_UNSUPPORTED: G would exceed 1 GiB. */
+int frt_deconvolve_create(frt_deconvolve** h, const double* x, int64_t Lx, int refs, int64_t n, double reg, const double* reg_bins);
+void frt_deconvolve_destroy(frt_deconvolve* h);
+/* Launches go to the null stream unless another one is set here. */
+int frt_deconvolve_set_stream(frt_deconvolve* h, void* hip_stream);
+/* One call over `rows` measured rows of T samples: y float32 (y_dtype 0) or float64 (1), sample t of row r is y[r row_stride + t].
+ * out[r out_stride + t], t < keep: h.  spectrum: NULL, or H [rows][n/2 + 1] (re, im).  Host or device buffers in any mix
+ * (host ones are staged); one synchronisation at the end.  FRT_ERR_INVALID, before any device call: a null handle, null y or
+ * out, an unknown y_dtype, rows outside 1 .. 65535, a handle of neither 1 nor `rows` references, T or keep outside 1 .. n, a
+ * bad stride, scratch_bytes < 0. */
+int frt_deconvolve_run(frt_deconvolve* h, const void* y, int y_dtype, int rows, int64_t T, int64_t row_stride, int64_t keep,
+                       int64_t scratch_bytes, double* out, int64_t out_stride, double* spectrum);
 
 #ifdef __cplusplus
 }
