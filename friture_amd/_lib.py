@@ -201,7 +201,14 @@ SIGNATURES = {
     "frt_deconvolve_destroy": (None, [c_void_p]),
     "frt_deconvolve_set_stream": (c_int, [c_void_p, c_void_p]),
     "frt_deconvolve_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
-    "frt_lfilter_f64": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
+    "frt_mtf_tile": (c_int, []),
+    "frt_mtf_create": (c_int, [POINTER(c_void_p), c_double, POINTER(c_double), c_int]),
+    "frt_mtf_destroy": (None, [c_void_p]),
+    "frt_mtf_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_mtf_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "frt_sti_run": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_void_p]),
+    "frt_lfilter_f64":(c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }
 

@@ -41,6 +41,7 @@ EXTRA_FLAGS = {"iir.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-for
                "convolve.hip": ["-ffp-contract=off"],        # X2 fixes its fused multiply-adds itself: every other product rounds on its own
                "decay.hip": ["-ffp-contract=off"],           # X3: e[t] is a rounded square, then added
                "deconvolve.hip": ["-ffp-contract=off"],      # X4: every product of the transform and of Y G rounds on its own
+               "mtf.hip": ["-ffp-contract=off"],             # X5: the fused multiply-adds of the sums are the ones written out
                "stft.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"]}
 
 

@@ -1014,6 +1014,66 @@ int frt_deconvolve_set_stream(frt_deconvolve* h, void* hip_stream);
 int frt_deconvolve_run(frt_deconvolve* h, const void* y, int y_dtype, int rows, int64_t T, int64_t row_stride, int64_t keep,
                        int64_t scratch_bytes, double* out, int64_t out_stride, double* spectrum);
 
+/* ---- X5: modulation transfer of impulse responses and the Speech Transmission Index (MtfBatch, sti_from_mtf) ---------------
+ * The reference has no such component; this is the definition (IEC 60268-16:2011, Schroeder's indirect method).
+ * Modulation transfer.  A row x[0 .. T) is float32 or float64, 1 <= T <= 2^24; all arithmetic is float64, e[t] = (double)x[t]^2.
+ * A handle holds fs (default 48000, 100 .. 1e7) and nf modulation frequencies F_j in Hz, 1 <= nf <= 16, 0 < F_j < fs / 2.  Per
+ * row, over the interval [start, stop) with 0 <= start < stop <= T (default 0, T):
+ *    S0 = sum e[t];  S_j = sum e[t] exp(-2 pi i F_j t / fs), t counted from the row's sample 0;  m_j = |S_j| / S0.
+ * Outputs per row: m [nf] and energy = S0.  A row that is all zero over the interval, or holds a sample there that is not
+ * finite, gives NaN in m (energy is then 0, NaN or inf); it never faults and never affects its neighbours.  A row whose
+ * interval is not one (which only device arrays can carry this far) is dead: NaN in m and in energy.
+ * Order of the sums, per row and anchored at its sample 0 (so the bits of a row depend on its own samples, start, stop and
+ * the frequencies: on no other row, on no slab size, row stride or input dtype, and not on host against device buffers):
+ * tiles of frt_mtf_tile() = 4096 samples; lane l of a 64-lane wavefront holds the samples t = 4096 J + 64 q + l, q = 0 .. 63, of
+ * tile J, and exp(-2 pi i F_j t / fs) is never evaluated: it is the product coarse_j[J] lane_j[l] step_j[q] of three table
+ * entries, each exp(-2 pi i F_j u / fs) at u = 4096 J, l, 64 q, made on the host in long double from the exactly reduced
+ * fractional part of F_j u / fs and rounded once.  Samples outside [start, stop) count as e = 0.  Per lane and frequency a =
+ * sum_q e[q] step[q] as fused multiply-adds onto 0, real and imaginary part each, the even q and the odd q as two chains (q
+ * ascending) whose sums are added at the end; s0 = s0 + e[q], q ascending.  Per tile: a lane[l] as a complex product whose
+ * four products round on their own (re: a.re u.re - a.im u.im, im: a.re u.im + a.im u.re), the 64 lanes folded by a butterfly
+ * (v += v of lane xor 32, 16, .. 1), the sum times coarse[J] in the same way; s0 folded likewise.  Per row: lane i of a
+ * wavefront adds the tile values of tiles J0 + i, J0 + i + 64, .. in order, J0 = floor(start / 4096), the lanes folded by the
+ * same butterfly; m_j = sqrt(re^2 + im^2) / S0.  No atomics, no contraction besides the fma above.
+ * Index from m [S][7][nf], the octave bands 1000 G^k, k = -3 .. 3, G = 10^0.3 (125 Hz .. 8 kHz), one wavefront per response:
+ * 1. Corrections, at most one: snr_db [S][7]: m' = m / (1 + 10^(-snr / 10)).  Or absolute octave-band levels level_db [S][7]
+ *    with noise_db [S][7] (or none: In = 0): I_k = 10^(L_k / 10), In_k = 10^(N_k / 10), Irt_k = 10^(A_k / 10) with the reception
+ *    thresholds A = 46, 27, 12, 6.5, 7.5, 8, 12 dB; Iam_1 = 0 and for k > 1 Iam_k = (I_{k-1} + In_{k-1}) 10^(amdB(Ltot_{k-1}) / 10),
+ *    Ltot = 10 log10(I + In), amdB(L) = 0.5 L - 65 below 63 dB, 1.8 L - 146.9 below 67 dB, 0.5 L - 59.8 below 100 dB, -10 from
+ *    there; m' = m I_k / (I_k + In_k + Iam_k + Irt_k).
+ * 2. snr_eff = 10 log10(m' / (1 - m')) clipped to [-15, 15] (m' >= 1: 15, m' <= 0: -15); TI = (snr_eff + 15) / 30.
+ * 3. MTI_k = the mean of TI over the columns of band k that the mask [7][nf] names, added with j ascending.
+ * 4. STI = sum alpha_k MTI_k - sum beta_k sqrt(MTI_k MTI_{k+1}), k ascending, at most 1.  A NaN in a used m makes that
+ *    response's STI NaN and no other's.
+ * Out of scope: the direct method (STIPA test-signal generation and the analysis of a recording of it), IEC 61260 IIR band
+ * filters, the changes of the standard's revision 5, absolute levels from an uncalibrated response, a carried state, sample
+ * rates handled in any way other than the fs argument. */
+typedef struct frt_mtf frt_mtf;
+/* pure host: the tile length of the sums */
+int frt_mtf_tile(void);
+/* freqs: [nf] HOST doubles.  The tables are made here, on the host.  FRT_ERR_INVALID, before any device call: a null handle
+ * pointer or null freqs, fs outside 100 .. 1e7, nf outside 1 .. 16, a frequency outside (0, fs / 2), anything not finite. */
+int frt_mtf_create(frt_mtf** h, double fs, const double* freqs, int nf);
+void frt_mtf_destroy(frt_mtf* h);
+/* Launches go to the null stream unless another one is set here. */
+int frt_mtf_set_stream(frt_mtf* h, void* hip_stream);
+/* One call over `rows` rows of n samples.  x: float32 (x_dtype 0) or float64 (1), sample t of row r is x[r row_stride + t]
+ * (stride in elements, >= n).  start, stop: [rows] or NULL (0, n).  m [rows][nf], energy [rows].  The rows are cut into slabs
+ * whose scratch ((1 + 2 nf) doubles per tile) stays within scratch_bytes (at least one row per launch); the result does not
+ * depend on it.  Host or device buffers in any mix (host ones are staged); one synchronisation at the end.
+ * FRT_ERR_INVALID, before any launch: a null handle, an unknown x_dtype, rows outside 1 .. 65535, n outside 1 .. 2^24, a null
+ * x, a bad stride, scratch_bytes < 0, a null output, and in host arrays a start outside 0 .. n - 1, a stop outside 1 .. n or
+ * (with both known on the host) a start that is not below its stop. */
+int frt_mtf_run(frt_mtf* h, const void* x, int x_dtype, int rows, int64_t n, int64_t row_stride, const int64_t* start,
+                const int64_t* stop, int64_t scratch_bytes, double* m, double* energy);
+/* Steps 1 to 4 over `responses` responses.  correction 0: a and b are NULL; 1: a = snr_db; 2: a = level_db, b = noise_db or
+ * NULL.  alpha [7], beta [6] and mask [7][nf] (bytes, non-zero: the column counts) are HOST arrays.  sti [responses], mti
+ * [responses][7], ti [responses][7][nf].  m, a, b and the outputs: host or device buffers in any mix; launched on hip_stream
+ * (NULL: the null stream), synchronised.  FRT_ERR_INVALID, before any device call: responses outside 1 .. 2^24, nf outside
+ * 1 .. 16, an unknown correction, arrays that do not fit it, a null buffer, a band without a column in the mask. */
+int frt_sti_run(const double* m, int responses, int nf, int correction, const double* a, const double* b, const double* alpha,
+                const double* beta, const unsigned char* mask, double* sti, double* mti, double* ti, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
