@@ -540,6 +540,7 @@ extern "C" int frt_decay_run(frt_decay* h, const void* x, int x_dtype, int rows,
     const long long all_groups = (p.ntile + kWaves - 1) / kWaves;
     for (long long r0 = 0; r0 < R; r0 += slab) {
         const unsigned nr = (unsigned)std::min(slab, R - r0);
+        // tests/test_decay_edges_gpu.py (the tile loops' second trip) derives its shapes from this formula: change both together
         const unsigned tile_groups = (unsigned)std::min(all_groups, std::max(16LL, (8192 + nr - 1) / (long long)nr));
         Call c = p;
         c.x = x0 + (size_t)r0 * (size_t)p.row_stride * xsize;

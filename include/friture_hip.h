@@ -907,7 +907,8 @@ int frt_irfft_rows(const double* spec, int64_t rows, int n, double* out, void* h
  * 3. Noise: nb = floor(T / W) blocks, q[k] = the sum of e over [k W, (k + 1) W); nt = max(1, ceil(noise_tail nb));
  *    N0 = (the sum of the last nt block sums) / (nt W), 0 when nb = 0.
  * 4. Truncation: auto: t1 = k W for the smallest k > floor(p / W) with q[k] <= W N0 10^(margin_db / 10), T if there is none;
- *    none: t1 = T; or given per row, t0 < t1 <= T.
+ *    none: t1 = T; or given per row, t0 < t1 <= T.  A row whose given onset lies at or behind its automatic truncation
+ *    (t1 <= t0) is a dead row.
  * 5. Schroeder integral and decay curve, t0 <= t < t1: E[t] = e[t] + .. + e[t1 - 1], L[t] = 10 log10(E[t] / E[t0]).
  * 6. Decay times over the ranges (hi, lo): EDT (0, -10), T10 (-5, -15), T20 (-5, -25), T30 (-5, -35).  a = the smallest t
  *    with L[t] <= hi (EDT: a = t0), b = the smallest t with L[t] <= lo; a least-squares line of L[t] over k = t - a, a <= t < b

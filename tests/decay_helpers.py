@@ -1,5 +1,6 @@
 """What the DecayBatch tests share: the numpy restatement of X3 (include/friture_hip.h, steps 1 to 9) in float64 or
 np.longdouble, seeded responses, the gap condition on the reference and the two distances."""
+import functools
 import math
 
 import numpy as np
@@ -68,6 +69,8 @@ def restate(x, fs=48000, block=480, onset_db=-20.0, noise_tail=0.1, margin_db=10
             gap_q = float(np.min(np.abs(q[first:last + 1] - bound) / bound))
     else:
         t1 = int(truncate)
+    if onset is not None and isinstance(truncate, str) and t1 <= t0:
+        return _dead(T, curve_step)                                  # step 4: a given onset at or behind the automatic truncation
     assert 0 <= t0 < t1 <= T
     seg = e[t0:t1]
     E = np.cumsum(seg[::-1])[::-1]
@@ -175,3 +178,140 @@ def compare(res, refs, label, db_bar=1e-9, rel_bar=1e-8, curve_bar=1e-9):
     for f in INDICES:
         assert np.array_equal(np.asarray(getattr(res, f)), column(refs, f)), f"{label}: {f} {getattr(res, f)} != {column(refs, f)}"
     assert worst_db <= db_bar and worst_rel <= rel_bar and worst_r2 <= rel_bar and worst_curve <= curve_bar, line
+
+
+# ---- the cases of test_decay_edges_gpu.py, proven on the reference alone by test_decay_edges_cpu.py ------------------------------
+
+TILE = 512                                  # decay.TILE
+LEADS = (0, TILE - 1, TILE)
+EDGE_T = 5 * TILE + 17
+EDGE_BLOCKS = (8, 9, 63, 64, 65, 100, 512, 513, 1000, 2577, 65536)
+EDGE_FS = (8000, 11025, 44100, 96000, 192000)
+EDGE_SETTINGS = tuple([("onset_db", v) for v in (0.0, -6.0, -40.0, -60.0)] + [("noise_tail", v) for v in (0.001, 0.5, 1.0)] +
+                      [("margin_db", v) for v in (0.0, 3.0, 25.0)])
+STRIDED_T = 66 * TILE + 5
+STRIDED_LEADS = (0, TILE - 1, TILE, 3)
+STRIDED_ROWS = 520
+
+
+def strided(live_tiles, rows):
+    """Whether a wavefront of dk_totals / dk_scan (mtf_tiles) takes a second tile: a launch of `rows` rows holds
+    min(ceil(ntile / 4), max(16, ceil(8192 / rows))) workgroups of 4 wavefronts per row, and 4 ceil(ntile / 4) covers every tile."""
+    return live_tiles > 4 * max(16, -(-8192 // rows))
+
+
+def _frozen(x):
+    x.setflags(write=False)
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def block_case(W, f32):
+    """(x [rows, EDGE_T], the longdouble references at block=W, curve_step=7): the lead-ins 0, 511, 512 in turn, a decay of 60 dB
+    over half of what the lead-in leaves; 3 float64 rows or 65 float32 rows."""
+    rows = 65 if f32 else 3
+    x = np.stack([response(EDGE_T, 0.5 * (EDGE_T - LEADS[i % 3]) / 48000, 1000 * W + (100 if f32 else 0) + i, LEADS[i % 3],
+                           dtype=np.float32 if f32 else np.float64) for i in range(rows)])
+    refs = restate_rows(x, block=W, curve_step=7, real=np.longdouble)
+    check_gaps(refs)
+    return _frozen(x), refs
+
+
+def clarity_samples(fs):
+    return math.floor(0.05 * fs + 0.5), math.floor(0.08 * fs + 0.5)
+
+
+@functools.lru_cache(maxsize=None)
+def fs_case(fs, f32):
+    """(x [rows, 4 TILE + 100], the longdouble references at that fs, block=16, truncate="auto"): the lead-ins 37, 511, 512."""
+    T, rows, leads = 4 * TILE + 100, 65 if f32 else 3, (37, TILE - 1, TILE)
+    x = np.stack([response(T, 0.3 * T / fs, fs + (100 if f32 else 0) + i, leads[i % 3], fs=fs, dtype=np.float32 if f32 else np.float64)
+                  for i in range(rows)])
+    refs = restate_rows(x, fs=fs, block=16, real=np.longdouble)
+    check_gaps(refs)
+    return _frozen(x), refs
+
+
+@functools.lru_cache(maxsize=None)
+def fs_long_case(fs):
+    """(x [3, T], the onsets, the longdouble references at truncate=None): one float64 row three times, long enough for n80, with
+    the onset that step 2 finds, the next one that puts t0 + n50 on a multiple of TILE, and the next that puts it one before."""
+    n50, n80 = clarity_samples(fs)
+    T = n80 + 3 * TILE + 100
+    row = response(T, 0.3 * T / fs, fs, 37, fs=fs)
+    t0 = restate(row, fs=fs, block=16, truncate=None)["onset"]
+    on_seam = t0 + (-(t0 + n50)) % TILE
+    before_seam = t0 + (TILE - 1 - (t0 + n50)) % TILE
+    onset = np.array([t0, on_seam, before_seam], np.int64)
+    x = np.stack([row] * 3)
+    refs = restate_rows(x, onset=onset, truncate=None, fs=fs, block=16, real=np.longdouble)
+    check_gaps(refs)
+    return _frozen(x), _frozen(onset), refs
+
+
+@functools.lru_cache(maxsize=None)
+def setting_case(name, value, f32):
+    """(x [3, EDGE_T], the longdouble references at block=16 and that one setting): a lead-in of 300; the seeds are 5, 15, 25
+    for onset_db, 6, 16, 26 for noise_tail (at noise_tail = 1 seed 5 ends on a sample small enough to reach -35 dB) and 7, 17, 27
+    for margin_db."""
+    first = {"onset_db": 5, "noise_tail": 6, "margin_db": 7}[name]
+    x = np.stack([response(EDGE_T, 0.5 * EDGE_T / 48000, first + 10 * i, 300, dtype=np.float32 if f32 else np.float64) for i in range(3)])
+    refs = restate_rows(x, block=16, real=np.longdouble, **{name: value})
+    check_gaps(refs)
+    return _frozen(x), refs
+
+
+@functools.lru_cache(maxsize=None)
+def strided_case():
+    """(the probes [4, 66 TILE + 5] float32, their longdouble references at block=16, truncate=None, curve_step=7): live spans
+    of 67 and 66 tiles."""
+    T = STRIDED_T
+    x = np.stack([response(T, 0.8 * T / 48000, 9000 + i, lead, dtype=np.float32) for i, lead in enumerate(STRIDED_LEADS)])
+    refs = restate_rows(x, block=16, truncate=None, curve_step=7, real=np.longdouble)
+    check_gaps(refs)
+    return _frozen(x), refs
+
+
+def live_tiles(onset, truncation, tile=TILE):
+    return (np.asarray(truncation) - 1) // tile - np.asarray(onset) // tile + 1
+
+
+@functools.lru_cache(maxsize=None)
+def live_span_case():
+    """(x [6, STRIDED_T], onsets, truncations, references): probe rows with given onsets and truncations that leave exactly 64 and
+    65 live tiles, starting in tile 0 and in tile 1, on a tile's first sample and inside it."""
+    probes, _ = strided_case()
+    pairs = [(1, TILE, 65 * TILE), (1, TILE, 65 * TILE + 1), (0, 0, 64 * TILE), (0, 0, 64 * TILE + 1), (3, 3, 64 * TILE - 5),
+             (2, TILE + 7, 65 * TILE + 9)]
+    x = np.stack([probes[i] for i, _, _ in pairs])
+    onset, truncation = (np.array([p[k] for p in pairs], np.int64) for k in (1, 2))
+    refs = restate_rows(x, onset=onset, truncate=truncation, block=16, curve_step=7, real=np.longdouble)
+    check_gaps(refs)
+    return _frozen(x), _frozen(onset), _frozen(truncation), refs
+
+
+@functools.lru_cache(maxsize=None)
+def dead_index_case():
+    """(x [7, 2 TILE + 3] of one response, onsets, truncations, the good row's number, its reference): six rows whose given onset
+    or truncation lies outside its range around one good row."""
+    T = 2 * TILE + 3
+    row = response(T, 0.5 * T / 48000, 4242)
+    onset = np.array([-1, T, 5, 5, 5, 700, 700], np.int64)
+    truncation = np.array([T, T, 0, T - 100, T + 1, 700, 100], np.int64)
+    good = 3
+    ref = restate(row, onset=5, truncate=T - 100, block=16, curve_step=7, real=np.longdouble)
+    check_gaps([ref])
+    return _frozen(np.stack([row] * 7)), _frozen(onset), _frozen(truncation), good, ref
+
+
+@functools.lru_cache(maxsize=None)
+def late_onset_case():
+    """(x [5, EDGE_T], onsets, references at block=16, truncate="auto", curve_step=7): rows 1 and 3 are given an onset at and
+    behind their automatic truncation and are dead; rows 0, 2 and 4 are given the onset that step 2 finds."""
+    x = np.stack([response(EDGE_T, 0.5 * (EDGE_T - LEADS[i % 3]) / 48000, 777 + i, LEADS[i % 3]) for i in range(5)])
+    found = restate_rows(x, block=16, real=np.longdouble)
+    onset = np.array([r["onset"] for r in found], np.int64)
+    onset[1], onset[3] = found[1]["truncation"], found[3]["truncation"] + 5
+    refs = restate_rows(x, onset=onset, block=16, curve_step=7, real=np.longdouble)
+    check_gaps([refs[i] for i in (0, 2, 4)])
+    return _frozen(x), _frozen(onset), refs

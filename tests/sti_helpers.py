@@ -161,3 +161,56 @@ def compare(res, ref, label, m_bar=1e-10, energy_bar=1e-10):
     line = f"{label}: m {dm:.3g} (bar {m_bar:g}), energy {de:.3g} relative (bar {energy_bar:g})"
     print(line)
     assert dm <= m_bar and de <= energy_bar, line
+
+
+# ---- the cases of test_sti_edges_gpu.py, proven on the reference alone by test_sti_edges_cpu.py ----------------------------------
+
+TILE = 4096                                 # sti.TILE
+LEADS = (0, TILE - 1, TILE)
+EDGE_T = 2 * TILE + 3
+OFF_DEFAULT = ((44100, (0.63, 3.15, 12.5, 997.0, 22049.5)), (100, (0.63, 7.3, 49.9)), (96000, (0.001, 1.0, 47999.0)),
+               (22050.5, (0.63, 3.0, 10000.25)), (48000, MOD_FREQS[-9:]))
+STRIDED_T = 66 * TILE + 5
+STRIDED_LEADS = (0, TILE - 1, TILE, 3)
+STRIDED_ROWS = 520
+
+
+def _frozen(x):
+    x.setflags(write=False)
+    return x
+
+
+def seam_rows(T, rows, f32):
+    """[rows, T] with the lead-ins 0, TILE - 1, TILE in turn and decays that fall 60 dB over what the lead-in leaves."""
+    return _frozen(np.stack([response(T, (T - LEADS[i % 3]) / 48000, 1000 * T + i, LEADS[i % 3], dtype=np.float32 if f32 else np.float64)
+                             for i in range(rows)]))
+
+
+@functools.lru_cache(maxsize=None)
+def off_default_case(fs, freqs, f32):
+    """(x [3, EDGE_T], the longdouble reference at that fs and those frequencies): the lead-ins 0, TILE - 1, TILE."""
+    x = np.stack([response(EDGE_T, (EDGE_T - lead) / 48000, 7000 + (100 if f32 else 0) + i, lead, dtype=np.float32 if f32 else np.float64)
+                  for i, lead in enumerate(LEADS)])
+    return _frozen(x), restate_mtf(x, freqs, fs, real=np.longdouble)
+
+
+@functools.lru_cache(maxsize=None)
+def strided_case():
+    """(the probes [4, 66 TILE + 5] float32, start = their lead-ins, the longdouble reference over [start, T) at the defaults):
+    live spans of 67 and 66 tiles."""
+    T = STRIDED_T
+    x = np.stack([response(T, 2 * (T - lead) / 48000, 9100 + i, lead, dtype=np.float32) for i, lead in enumerate(STRIDED_LEADS)])
+    start = np.array(STRIDED_LEADS, np.int64)
+    return _frozen(x), _frozen(start), restate_mtf(x, start=start, real=np.longdouble)
+
+
+@functools.lru_cache(maxsize=None)
+def live_span_case():
+    """(x [6, STRIDED_T], start, stop, the reference): probe rows over intervals of exactly 64 and 65 live tiles, from tile 0 and
+    from tile 1, from a tile's first sample and from inside it."""
+    probes, _, _ = strided_case()
+    pairs = [(2, TILE, 65 * TILE), (2, TILE, 65 * TILE + 1), (0, 0, 64 * TILE), (0, 0, 64 * TILE + 1), (3, 3, 64 * TILE - 5),
+             (1, TILE + 7, 65 * TILE + 9)]
+    x = np.stack([probes[i] for i, _, _ in pairs])
+    start, stop = (np.array([p[k] for p in pairs], np.int64) for k in (1, 2))
+    return _frozen(x), _frozen(start), _frozen(stop), restate_mtf(x, start=start, stop=stop, real=np.longdouble)
