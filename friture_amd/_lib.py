@@ -208,6 +208,14 @@ SIGNATURES = {
     "frt_mtf_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "frt_sti_run": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p,
                             c_void_p, c_void_p, c_void_p]),
+    "frt_sos_default_cell": (c_int, []),
+    "frt_sos_state_length": (c_int, [c_int]),
+    "frt_sos_tables": (c_int, [POINTER(c_double), c_int, c_int, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
+    "frt_sos_create": (c_int, [POINTER(c_void_p), POINTER(c_double), c_int, c_int, c_int]),
+    "frt_sos_destroy": (None, [c_void_p]),
+    "frt_sos_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_sos_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_int64,
+                            c_void_p, c_int]),
     "frt_lfilter_f64":(c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

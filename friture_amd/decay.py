@@ -27,11 +27,13 @@ Parameters: block W = 480 samples (10 ms at 48 kHz; any integer in 8 .. 65536), 
 9. keep=("params", "curve") with curve_step= gives L[t0 + j step] as float64 [R, ceil(T / step)]; entries past t1 are NaN.
 The bits of a row do not depend on the other rows of the call, on scratch_bytes, on a row stride or on the input's dtype (the
 order of the sums: X3).  Out of scope: a carried state (a decay is integrated from its end, so a response is given whole),
-Lundeby's iteration, the tail-compensation term, noise subtraction, IIR band filters per IEC 61260 class, sample rates handled
-in any way other than the fs argument.  There is no CPU fallback: run() goes to the HIP library.
+Lundeby's iteration, the tail-compensation term, noise subtraction, sample rates handled in any way other than the fs argument
+(IIR band filters: room_acoustics(filters="butterworth"), X6, friture_amd/sosfilter.py).  There is no CPU fallback: run() goes to the HIP library.
 
 The band front (band_edges, band_filter, room_acoustics) is composition: a Kaiser-windowed linear-phase FIR per band, designed
-on the host, applied by ConvolveBatch, its delay cut off by a strided view that DecayBatch reads in place."""
+on the host, applied by ConvolveBatch, its delay cut off by a strided view that DecayBatch reads in place; or, with
+filters="butterworth" / "butterworth-reversed", Butterworth band-passes on the IEC 61260-1 base-ten band edges run as one bank
+by SosBatch."""
 from __future__ import annotations
 
 import ctypes
@@ -181,16 +183,43 @@ def band_filter(f_lo, f_hi, fs=48000, attenuation_db=60.0, transition=0.25):
     return (2 * hi * np.sinc(2 * hi * n) - 2 * lo * np.sinc(2 * lo * n)) * np.kaiser(2 * M + 1, beta)
 
 
-def room_acoustics(ir, bands="octave", fs=48000, **decay_settings):
+def _per_band(v, B):
+    """A per-response vector [S] (or a scalar) with every entry B times in a row: [S B], numpy or tensor as it came."""
+    if hasattr(v, "repeat_interleave"):
+        return v.reshape(-1).repeat_interleave(B)
+    return np.repeat(np.asarray(v).reshape(-1), B)
+
+
+FILTERS = ("fir", "butterworth", "butterworth-reversed")
+
+
+def room_acoustics(ir, bands="octave", fs=48000, filters="fir", order=3, **decay_settings):
     """The broadband and per-band decay of responses ir [S, T] or [T]: RoomResult(centres [B], broadband, bands), two
     DecayResults, every field of `bands` with a band axis behind the response axis ([S, B]; r2 [S, B, 4]).  One broadband
-    DecayBatch.run finds the onsets; per band, ConvolveBatch(band_filter(..)).run(ir).y[..., M : M + T] is read in place with
-    those onsets.  decay_settings: DecayBatch's parameters, and truncate / scratch_bytes of its run()."""
+    DecayBatch.run finds the onsets.  filters="fir": per band, ConvolveBatch(band_filter(..)).run(ir).y[..., M : M + T] is read in
+    place with those onsets.  filters="butterworth": Butterworth band-passes of `order` on the same band edges
+    (sosfilter.band_sos); one bank run of SosBatch gives [S, B, T] in float64 and its [S B, T] view goes through one
+    DecayBatch.run with the broadband onsets repeated: no loop over the bands and no delay to cut.  "butterworth-reversed" runs
+    the bank backwards in time (ISO 3382: a band's own ringing then lies in front of the decay, not on it).  decay_settings:
+    DecayBatch's parameters, and truncate / scratch_bytes of its run()."""
+    if filters not in FILTERS:
+        raise ValueError(f"filters={filters!r} ({', '.join(repr(f) for f in FILTERS)})")
     run_settings = {k: decay_settings.pop(k) for k in ("truncate", "scratch_bytes") if k in decay_settings}
     centres, edges = band_edges(bands)
     db = DecayBatch(fs=fs, **decay_settings)
     broadband = db.run(ir, **run_settings)
     T = ir.shape[-1]
+    if filters != "fir":
+        from . import sosfilter
+        B = len(centres)
+        sos = np.stack([sosfilter.butter_band_sos(f_lo, f_hi, fs, order) for f_lo, f_hi in edges])
+        y = sosfilter.SosBatch(sos).run(ir, fan=True, reverse=filters == "butterworth-reversed", dtype="float64").y
+        if not (run_settings.get("truncate") is None or isinstance(run_settings["truncate"], str)):
+            run_settings["truncate"] = _per_band(run_settings["truncate"], B)
+        res = db.run(y.reshape(-1, T), onset=_per_band(broadband.onset, B), **run_settings)
+        lead = tuple(ir.shape[:-1]) + (B,)
+        fields = [None if v is None else v.reshape(lead + tuple(v.shape[1:])) for v in res]
+        return RoomResult(centres, broadband, DecayResult(*fields))
     per_band = []
     for f_lo, f_hi in edges:
         h = band_filter(f_lo, f_hi, fs)

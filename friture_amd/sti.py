@@ -22,12 +22,13 @@ STI from m [S, 7, nf], the octave bands 1000 G^k, k = -3 .. 3, G = 10^0.3 (125 H
    column is refused.
 4. STI = sum alpha_k MTI_k - sum beta_k sqrt(MTI_k MTI_{k+1}), at most 1.  A NaN in any used m makes that response's STI NaN
    and no other.
-Out of scope: the direct method (STIPA test-signal generation and the analysis of a recording of it), IEC 61260 IIR band
-filters, revision 5's changes, absolute levels derived from an uncalibrated response, a carried state, sample rates handled
+Out of scope: the direct method (STIPA test-signal generation and the analysis of a recording of it), revision 5's changes
+(IIR band filters: speech_transmission(filters="butterworth"), X6, friture_amd/sosfilter.py), absolute levels derived from an uncalibrated response, a carried state, sample rates handled
 in any way other than the fs argument.  There is no CPU fallback: run() and sti_from_mtf() go to the HIP library.
 
 speech_transmission is composition like room_acoustics: DecayBatch finds onset and truncation, ConvolveBatch applies
-decay.band_filter per octave, MtfBatch reads the delayed view in place, sti_from_mtf finishes."""
+decay.band_filter per octave, MtfBatch reads the delayed view in place, sti_from_mtf finishes; with filters="butterworth" /
+"butterworth-reversed" the seven octaves are Butterworth band-passes run as one bank by SosBatch."""
 from __future__ import annotations
 
 import ctypes
@@ -231,15 +232,28 @@ def speech_levels(laeq, voice="male"):
     return float(laeq) + np.array(SPEECH_SPECTRUM_DB[voice])
 
 
-def speech_transmission(ir, fs=48000, truncate="auto", **corrections):
+def speech_transmission(ir, fs=48000, truncate="auto", filters="fir", order=3, **corrections):
     """The Speech Transmission Index of responses ir [S, T] or [T]: SpeechResult(centres [7], sti [S], mti [S, 7], ti [S, 7, 14],
     m [S, 7, 14]) at MOD_FREQS.  One broadband DecayBatch.run gives the onset and the truncation (truncate=None: the whole row
-    behind the onset); per octave band, ConvolveBatch(band_filter(..)).run(ir).y[..., M : M + T] is read in place by MtfBatch with
-    start = onset, stop = truncation; then sti_from_mtf(m, **corrections) (snr_db, level_db, noise_db, weights, scheme)."""
+    behind the onset).  filters="fir": per octave band, ConvolveBatch(band_filter(..)).run(ir).y[..., M : M + T] is read in place
+    by MtfBatch with start = onset, stop = truncation.  filters="butterworth" / "butterworth-reversed": one bank run of SosBatch
+    over the seven Butterworth band-passes of `order` (sosfilter.band_sos, forward or backwards in time) gives [S, 7, T] in
+    float64, whose [7 S, T] view goes through one MtfBatch.run.  Then sti_from_mtf(m, **corrections) (snr_db, level_db, noise_db,
+    weights, scheme)."""
+    if filters not in decay.FILTERS:
+        raise ValueError(f"filters={filters!r} ({', '.join(repr(f) for f in decay.FILTERS)})")
     centres, edges = decay.band_edges(octave_bands())
     broadband = decay.DecayBatch(fs=fs).run(ir, truncate=truncate)
     mtf = MtfBatch(MOD_FREQS, fs)
     T = ir.shape[-1]
+    if filters != "fir":
+        from . import sosfilter
+        sos = np.stack([sosfilter.butter_band_sos(f_lo, f_hi, fs, order) for f_lo, f_hi in edges])
+        y = sosfilter.SosBatch(sos).run(ir, fan=True, reverse=filters == "butterworth-reversed", dtype="float64").y
+        m = mtf.run(y.reshape(-1, T), start=decay._per_band(broadband.onset, BANDS), stop=decay._per_band(broadband.truncation, BANDS)).m
+        m = m.reshape(tuple(ir.shape[:-1]) + (BANDS, len(MOD_FREQS)))
+        res = sti_from_mtf(m, **corrections)
+        return SpeechResult(centres, res.sti, res.mti, res.ti, m)
     per_band = []
     for f_lo, f_hi in edges:
         h = decay.band_filter(f_lo, f_hi, fs)

@@ -930,8 +930,8 @@ int frt_irfft_rows(const double* spec, int64_t rows, int n, double* out, void* h
  * defined index.  The regression sums: per tile lane sums in sample order folded by a butterfly, tile sums 64 apart added
  * in order and folded by a butterfly.  No atomics.
  * There is no carried state: a decay is integrated from its end, so a response is given whole.  Out of scope as well:
- * Lundeby's iteration, the tail-compensation term, noise subtraction, IIR band filters per IEC 61260 class, sample rates
- * handled in any way other than the fs argument. */
+ * Lundeby's iteration, the tail-compensation term, noise subtraction, sample rates handled in any way other than the fs
+ * argument.  IIR band filters in front of it (Butterworth band-passes on the same band edges) are X6. */
 typedef struct frt_decay frt_decay;
 /* pure host: the tile length of the scan */
 int frt_decay_tile(void);
@@ -1046,9 +1046,9 @@ int frt_deconvolve_run(frt_deconvolve* h, const void* y, int y_dtype, int rows, 
  * 3. MTI_k = the mean of TI over the columns of band k that the mask [7][nf] names, added with j ascending.
  * 4. STI = sum alpha_k MTI_k - sum beta_k sqrt(MTI_k MTI_{k+1}), k ascending, at most 1.  A NaN in a used m makes that
  *    response's STI NaN and no other's.
- * Out of scope: the direct method (STIPA test-signal generation and the analysis of a recording of it), IEC 61260 IIR band
- * filters, the changes of the standard's revision 5, absolute levels from an uncalibrated response, a carried state, sample
- * rates handled in any way other than the fs argument. */
+ * Out of scope: the direct method (STIPA test-signal generation and the analysis of a recording of it; IIR octave band-passes
+ * in front of the kernel are X6), the changes of the standard's revision 5, absolute levels from an uncalibrated response, a
+ * carried state, sample rates handled in any way other than the fs argument. */
 typedef struct frt_mtf frt_mtf;
 /* pure host: the tile length of the sums */
 int frt_mtf_tile(void);
@@ -1074,6 +1074,62 @@ int frt_mtf_run(frt_mtf* h, const void* x, int x_dtype, int rows, int64_t n, int
  * 1 .. 16, an unknown correction, arrays that do not fit it, a null buffer, a band without a column in the mask. */
 int frt_sti_run(const double* m, int responses, int nf, int correction, const double* a, const double* b, const double* alpha,
                 const double* beta, const unsigned char* mask, double* sti, double* mti, double* ti, void* hip_stream);
+
+/* ---- X6: IIR filters as cascades of second-order sections, and banks of them (SosBatch) ---------------------------------------
+ * The reference has no such component; this is the definition.
+ * A filter is K sections, 1 <= K <= 8, each [b0 b1 b2 a0 a1 a2]; the host divides by a0 (each quotient rounded once) and refuses
+ * a section with a pole |p| >= 1 (|a2| < 1 and |a1| < 1 + a2 must hold) or a coefficient that is not finite.  A handle holds F
+ * filters, 1 <= F <= 64, of the same K, and the cell size (below).  One sample x through one section, in float64, every product
+ * rounded on its own (no fused multiply-add):
+ *    y = b0 x + z0;   z0 = (b1 x - a1 y) + z1;   z1 = b2 x - a2 y
+ * and the sections run in order, y of one being x of the next: the operation order of scipy.signal.sosfilt.  float32 input
+ * widens exactly.  Output rows are (input row, filter):
+ *    bank mode (fan = 1): x [S][T] gives y [S][F][T], every input row through all F filters;
+ *    row mode  (fan = 0): x [R][T] gives y [R][T], row r through filter r mod F.
+ * reverse = 1 is flip(forward(flip(x))) from the zero state on whole rows: the index reflection t <-> T - 1 - t where x is read
+ * and y is written, nothing else; it takes and returns no state.  y is float64, or float32 as the one rounding of the float64 value.
+ * Time-parallel order.  A row is cut into cells of `cell` samples (a power of two in 32 .. 1024, chosen at creation) on a grid
+ * anchored at the stream's absolute sample index; 64 consecutive cells on that grid are a run.  With s the 2K states (z0, z1 of
+ * section 0, then of section 1, ..), M[i][j] = state i after `cell` samples of silence from the unit state j, and M^64 the same
+ * after 64 cells, both made on the host in long double by stepping the section code and rounded once:
+ *    P_c = the state behind cell c run from the zero state;
+ *    Q_r = the cells of run r chained from zero: q <- M q + P_c, c ascending;
+ *    U_0 = 0, U_(r+1) = M^64 U_r + Q_r: the true state in front of run r + 1;
+ *    S_c = U_r for a run's first cell, otherwise S_(c+1) = M S_c + P_c: the true state in front of cell c;
+ *    y over cell c = the sections stepped sample by sample from S_c.
+ * A matrix-vector step is new_i = ((P_i + M[i][0] s_0) + M[i][1] s_1) + .., every product rounded on its own.  A stream of at
+ * most `cell` samples is therefore the sequential filter, bit for bit.  The bits of an output row depend on its own samples, its
+ * filter, the cell size and the absolute sample index: on no other row, slab size, row stride, input dtype, or host against
+ * device buffers, and not on how the stream was cut into calls.  The state behind n samples is, per output row, five vectors of
+ * 2K doubles (frt_sos_state_length): the running state at n (S_c itself when n lies on the grid), the partial zero-state run of
+ * the cell that holds n, S_c of that cell, the partial q of its run, U_r of its run; n itself travels beside it (n_before).
+ * A NaN or infinity in a row makes that row's outputs not finite from that sample on and leaves the other rows' bits alone.
+ * Out of scope: design families other than Butterworth band-passes (friture_amd/sosfilter.py), padding or steady-state initial
+ * conditions for zero-phase use, decimating banks, a live chunk object. */
+typedef struct frt_sos frt_sos;
+/* pure host: the cell size that cell = 0 stands for; the doubles of a state per output row (0: sections outside 1 .. 8) */
+int frt_sos_default_cell(void);
+int frt_sos_state_length(int sections);
+/* pure host: what a handle of this design would hold.  coef [filters][sections][5] (b0 b1 b2 a1 a2 after the division), M and
+ * M64 [filters][2 sections][2 sections]; each may be NULL.  The checks are those of frt_sos_create. */
+int frt_sos_tables(const double* sos, int filters, int sections, int cell, double* coef, double* M, double* M64);
+/* sos: [filters][sections][6] HOST doubles.  cell: 0 for the default.  FRT_ERR_INVALID, before any device call: a null
+ * pointer, filters outside 1 .. 64, sections outside 1 .. 8, a cell that is no power of two in 32 .. 1024, a coefficient that
+ * is not finite, a0 = 0, a pole with |p| >= 1. */
+int frt_sos_create(frt_sos** h, const double* sos, int filters, int sections, int cell);
+void frt_sos_destroy(frt_sos* h);
+/* Launches go to the null stream unless another one is set here. */
+int frt_sos_set_stream(frt_sos* h, void* hip_stream);
+/* One call over `rows` input rows of n samples, 1 <= n <= 2^24.  x: float32 (x_dtype 0) or float64 (1), sample t of row r is
+ * x[r row_stride + t] (stride in elements, >= n).  y: dense, [rows][n] (fan 0) or [rows][filters][n] (fan 1), float32 (y_dtype
+ * 0) or float64 (1).  n_before: the samples the streams have seen; state_in [output rows][frt_sos_state_length] or NULL (fresh
+ * streams, n_before 0); state_out likewise or NULL.  The rows are cut into slabs whose scratch stays within scratch_bytes (at
+ * least one row per launch); the result does not depend on it.  Host or device buffers in any mix (host ones are staged); one
+ * synchronisation at the end.  FRT_ERR_INVALID, before any launch: a null handle, x or y, an unknown dtype, rows outside
+ * 1 .. 65535, n outside 1 .. 2^24, a bad stride, fan or reverse other than 0 or 1, reverse with a state or n_before, n_before
+ * without state_in or negative, scratch_bytes < 0. */
+int frt_sos_run(frt_sos* h, const void* x, int x_dtype, int rows, int64_t n, int64_t row_stride, int fan, int reverse,
+                int64_t n_before, const double* state_in, double* state_out, int64_t scratch_bytes, void* y, int y_dtype);
 
 #ifdef __cplusplus
 }
