@@ -50,6 +50,7 @@ SIGNATURES = {
     "frt_stft_analyzelive_f64": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
     "frt_stft_frames_for": (c_int64, [c_void_p, c_int64]),
     "frt_stft_set_run_length": (c_int, [c_void_p, c_int]),
+    "frt_stft_set_persistent": (c_int, [c_void_p, c_int, c_int]),
     "frt_octbank_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int] + [POINTER(c_double)] * 6),
     "frt_octbank_destroy": (None, [c_void_p]),
     "frt_octbank_set_stream": (c_int, [c_void_p, c_void_p]),

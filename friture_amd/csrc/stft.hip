@@ -158,6 +158,26 @@ static int launch_big(int log2m, const StftArgs& a, hipStream_t stream) {
 }
 
 
+// resident workgroups per CU of the walk's four instances (frt_stft_create: never queried inside a launch)
+static int walk_blocks_per_cu(int shift, bool split, int* out) {
+    hipError_t e = hipErrorInvalidValue;
+    if (shift == 4) e = split ? hipOccupancyMaxActiveBlocksPerMultiprocessor(out, stft_kernel<Walk<float>, float, 9, 4, true>, 256, 0)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(out, stft_kernel<Walk<float>, float, 9, 4, false>, 256, 0);
+    if (shift == 2) e = split ? hipOccupancyMaxActiveBlocksPerMultiprocessor(out, stft_kernel<Walk<float>, float, 9, 2, true>, 256, 0)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(out, stft_kernel<Walk<float>, float, 9, 2, false>, 256, 0);
+    FRT_HIP_CHECK(e);
+    return FRT_OK;
+}
+
+// the walk (stft_kernel<Walk<float>, ...>): `blocks` workgroups stride over the lane groups
+template <int SHIFT>
+static int launch_walk(const StftArgs& a, int blocks, hipStream_t stream) {
+    if (a.out_nyq) hipLaunchKernelGGL((stft_kernel<Walk<float>, float, 9, SHIFT, true>), dim3(blocks), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((stft_kernel<Walk<float>, float, 9, SHIFT, false>), dim3(blocks), dim3(256), 0, stream, a);
+    FRT_HIP_CHECK(hipGetLastError());
+    return FRT_OK;
+}
+
 template <typename TIN, typename T, int LOG2M, int SHIFT>
 static int launch_one(const StftArgs& a, int blocks, hipStream_t stream) {
     using P = Pow2Plan<LOG2M>;
@@ -223,6 +243,8 @@ using namespace frt;
 struct frt_stft {
     int fft_size = 0, hop = 0, n_channels = 0, precision = 32, log2m = 0;
     int run_length = 0;
+    int persist_mode = -1, persist_blocks = 0;   // frt_stft_set_persistent
+    int walk_resident[2] = {0, 0};               // resident workgroups of the walk's instance on this device: [packed rows, split rows]
     bool force_generic = false;   // A/B and tests: a negative run length selects the generic kernel
     hipStream_t stream = nullptr;
     DeviceBuffer window, tw, twn, tws, weight, wimage, edge_pow, bin_pow, lut;
@@ -285,6 +307,15 @@ extern "C" int frt_stft_create(frt_stft** out, int fft_size, int hop, int n_chan
     while ((2 << l) < fft_size) ++l;   // M = 2^l
     h->log2m = l;
     int rc = precision == 32 ? build_tables<float>(h) : build_tables<double>(h);
+    // float32, N = 1024, hop N/2 or N/4: how many workgroups of the walk are resident at once (queried here, once: launches stay
+    // free of runtime queries and so capture-safe)
+    if (!rc && precision == 32 && fft_size == 1024 && (hop == 512 || hop == 256)) {
+        for (int split = 0; split < 2 && !rc; ++split) {
+            int per_cu = 0;
+            rc = walk_blocks_per_cu(hop * 8 / fft_size, split != 0, &per_cu);
+            h->walk_resident[split] = per_cu * device_cu_count();
+        }
+    }
     if (rc) {
         frt_stft_destroy(h);
         return rc;
@@ -321,6 +352,15 @@ extern "C" int frt_stft_set_run_length(frt_stft* h, int r) {
     FRT_REQUIRE(h, "frt_stft_set_run_length: null handle");
     h->run_length = r < 0 ? -r : r;
     h->force_generic = r < 0;
+    return FRT_OK;
+}
+
+extern "C" int frt_stft_set_persistent(frt_stft* h, int mode, int blocks) {
+    FRT_REQUIRE(h, "frt_stft_set_persistent: null handle");
+    FRT_REQUIRE(mode >= -1 && mode <= 1, "frt_stft_set_persistent: mode %d is not -1 (automatic), 0 (never) or 1 (always)", mode);
+    FRT_REQUIRE(blocks >= 0, "frt_stft_set_persistent: blocks %d < 0", blocks);
+    h->persist_mode = mode;
+    h->persist_blocks = blocks;
     return FRT_OK;
 }
 
@@ -514,6 +554,40 @@ static int stft_launch(frt_stft* h, int kind, const void* d_x, int64_t x_stride,
         FRT_REQUIRE(bgroups < (1ll << 31), "frt_stft_run: too many lane groups");
         a.n_groups = (int)bgroups;
         return h->precision == 32 ? launch_big<float>(h->log2m, a, stream) : launch_big<double>(h->log2m, a, stream);
+    }
+    // The walk (stft_kernel<Walk<float>, ...>): float32, N = 1024, register window (hop N/2 or N/4 on aligned 2-sample loads).  A resident grid
+    // whose waves stride over short runs with their constants loaded once.  Automatic (mode -1): when no run length is set, the
+    // register-window instance is the one chosen and the batch gives every resident wave at least kWalkMinTrips runs; a widget-sized
+    // or catch-up call keeps the geometry above.  Mode 1 (tests, sweeps): whenever the instance exists — before the ring instance —
+    // and a set run length is then the walk's, rounded down to whole rounds of the register window.
+    // kWalkRun: the walk's run length (a multiple of the register window's rounds: 2 at hop N/2, 4 at hop N/4).  Swept in the real
+    // kernel at 131 071 frames (profiles/headline_persistent_ab.txt): 2 / 4 / 8 / 12 / 16 / 22 / 32 / 64 frames run 0.115 / 0.112 / 0.110 /
+    // 0.109 / 0.107 / 0.115 / 0.119 / 0.118 ms against 0.113 ms of one run of 16 per lane group: short runs do not pay, the walk itself does.
+    // kWalkMinTrips: the runs a resident wave must get before the automatic choice takes the walk: one run of 16, the same 16 frames
+    // per wave as four runs of four (65 535 frames gain 3 to 6 %, 32 767 frames, under the bar, none).  kWalkAutomatic: whether the
+    // automatic choice ever takes it.
+    constexpr int kWalkRun = 16, kWalkMinTrips = 1;
+    constexpr bool kWalkAutomatic = true;
+    if (h->log2m == 9 && h->precision == 32 && h->persist_mode != 0 && (shift == 2 || shift == 4 || (shift == -1 && h->persist_mode == 1))) {
+        const int wshift = shift == -1 ? 4 : shift, nsets = 8 / wshift;
+        int resident = h->walk_resident[d_nyq ? 1 : 0];
+        if (h->persist_blocks > 0) resident = h->persist_blocks;
+        int wrun = kWalkRun;
+        if (h->persist_mode == 1 && h->run_length > 0) wrun = h->run_length > 64 ? 64 : h->run_length;
+        wrun = wrun / nsets * nsets;
+        if (wrun < nsets) wrun = nsets;
+        const long long rpc = (F + wrun - 1) / wrun, wgroups = rpc * h->n_channels;
+        const bool take = h->persist_mode == 1 ? resident > 0
+                                               : kWalkAutomatic && h->run_length == 0 && resident > 0 && wgroups >= (long long)kWalkMinTrips * resident * gpb;
+        if (take) {
+            FRT_REQUIRE(wgroups < (1ll << 31) - (long long)resident * gpb, "frt_stft_run: too many lane groups");
+            const long long need = (wgroups + gpb - 1) / gpb;
+            const int grid = (int)(need < resident ? need : resident);
+            a.run = wrun;
+            a.runs_per_channel = (int)rpc;
+            a.n_groups = (int)wgroups;
+            return wshift == 4 ? launch_walk<4>(a, grid, stream) : launch_walk<2>(a, grid, stream);
+        }
     }
     const long long rest = F - a.frame_base;
     a.runs_per_channel = (int)((rest + run - 1) / run);

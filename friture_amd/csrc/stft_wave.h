@@ -161,15 +161,31 @@ __device__ __forceinline__ uint32_t value_bits_hi(double v) { return (uint32_t)_
 #ifndef FRT_RING_WEIGHTS_IN_LDS
 #define FRT_RING_WEIGHTS_IN_LDS 0
 #endif
-template <typename TIN, typename T, int LOG2M, int SHIFT, bool SPLIT = false>
+// PERSIST: the WALK (float32 register-window instances of N = 1024 only: stft_kernel<Walk<float>, ...>).  The grid is as many workgroups
+// as are resident; every wavefront loads its constants once and then walks the lane groups first, first + stride, ... — runs of 16
+// frames (stft_launch: shorter runs, a narrower front of open addresses, measured slower; the constants once and the small grid pay).  A static
+// stride loop: no atomics, no flags, nothing that waits for another wavefront.  At a run's last frame — a compile-time variant of
+// the frame — the window multiply has read the whole register window: all eight slots are requested for the NEXT run's first
+// frame there and pinned in front of that frame's row stores like every prefetch, so a run boundary costs no wait of its own.
+// The walk is selected through the sample type, Walk<float> in place of float: every other instance keeps its template arguments
+// (tests/test_ring_waitcnt.py finds the ring instances by their mangled names) and, as the resource report shows, its code.
+template <typename TIN> struct Walk {};
+template <typename TIN> struct WalkTraits { using type = TIN; static constexpr bool walk = false; };
+template <typename TIN> struct WalkTraits<Walk<TIN>> { using type = TIN; static constexpr bool walk = true; };
+#ifndef FRT_WALK_MIN_WAVES
+#define FRT_WALK_MIN_WAVES 3
+#endif
+template <typename TIN_, typename T, int LOG2M, int SHIFT, bool SPLIT = false>
 __global__ void
 #if defined(FRT_WAVE_MIN_WAVES)
 __launch_bounds__((Pow2Plan<LOG2M>::TPF < 256 ? 256 : Pow2Plan<LOG2M>::TPF),
-                  (Pow2Plan<LOG2M>::TPF <= 64 ? (SHIFT < 0 ? FRT_RING_MIN_WAVES : sizeof(T) == 8 ? FRT_WAVE_MIN_WAVES_F64 : FRT_WAVE_MIN_WAVES) : 1))
+                  (Pow2Plan<LOG2M>::TPF <= 64 ? (WalkTraits<TIN_>::walk ? FRT_WALK_MIN_WAVES : SHIFT < 0 ? FRT_RING_MIN_WAVES : sizeof(T) == 8 ? FRT_WAVE_MIN_WAVES_F64 : FRT_WAVE_MIN_WAVES) : 1))
 #else
 __launch_bounds__((Pow2Plan<LOG2M>::TPF < 256 ? 256 : Pow2Plan<LOG2M>::TPF))
 #endif
 stft_kernel(const StftArgs a) {
+    using TIN = typename WalkTraits<TIN_>::type;
+    constexpr bool PERSIST = WalkTraits<TIN_>::walk;
     using P = Pow2Plan<LOG2M>;
     constexpr int M = P::M, TPF = P::TPF;            // M = N/2 complex points
     constexpr int BLOCK = TPF < 256 ? 256 : TPF;
@@ -207,12 +223,13 @@ stft_kernel(const StftArgs a) {
     const int i = tid - grp * TPF;
     C* buf = lds + grp * Lay::size(M);
 
-    const int gg = blockIdx.x * GPB + grp;
+    // (the walk moves gg, chan, run, f0 and nfr from run to run; every other instance sets them here once)
+    int gg = blockIdx.x * GPB + grp;
     const bool group_ok = gg < a.n_groups;
     const int ggc = group_ok ? gg : 0;
-    const int chan = ggc / a.runs_per_channel;
-    const int run = ggc - chan * a.runs_per_channel;
-    const long long f0 = a.frame_base + (long long)run * a.run;
+    int chan = ggc / a.runs_per_channel;
+    int run = ggc - chan * a.runs_per_channel;
+    long long f0 = a.frame_base + (long long)run * a.run;
     const long long left = a.n_frames - f0;
     int nfr = left > a.run ? a.run : (int)left;            // frames of this run (32-bit: the loop's compares stay scalar)
     if (!group_ok) nfr = 0;
@@ -220,6 +237,10 @@ stft_kernel(const StftArgs a) {
     if (a.kind == FRT_STFT_IMAGE) {
         for (int t = threadIdx.x; t < 256; t += BLOCK) lut_lds[t] = a.lut[t];
         __syncthreads();
+    }
+    if constexpr (PERSIST) {
+        static_assert(LOG2M == 9 && SHIFT > 0 && sizeof(T) == 4 && sizeof(TIN) == 4, "the walk: float32 register-window instances of N = 1024");
+        if (!group_ok) return;                             // more waves than runs: nothing to read, nothing to write (no barrier below)
     }
     if constexpr (WLDS) {
         const T* wsrc = (const T*)(a.kind == FRT_STFT_IMAGE ? a.wimage : a.weight);
@@ -234,6 +255,8 @@ stft_kernel(const StftArgs a) {
 
     const TIN* xc = (const TIN*)a.x + chan * a.x_stride;
     T* outc = (T*)a.out + chan * a.out_cstride;
+    const TIN* xnext = xc;                             // the walk: channel base and first frame of the wave's NEXT run
+    long long fnext = f0;
     // complex point of the frame that register slot j of this thread holds before the transform
     auto point = [&](int j) -> int { return i + j * TPF; };
 
@@ -303,10 +326,10 @@ stft_kernel(const StftArgs a) {
     };
 
     typedef T tv2 __attribute__((ext_vector_type(2)));     // a slot stays ONE 64-bit register pair from the load to the window multiply
-    auto load_slot = [&](long long f, int j) -> tv2 {
+    auto load_slot = [&](const TIN* base, long long f, int j) -> tv2 {
         // frame base (wave-uniform for one-wavefront frames: a scalar pointer) + one 32-bit lane offset + the slot as an
         // immediate: the load's address costs no vector instruction
-        const TIN* fb = xc + f * a.hop;
+        const TIN* fb = base + f * a.hop;
         const unsigned lane_off = 2u * (unsigned)point(0);
         const int slot_off = 2 * (point(j) - point(0));
         if (SHIFT != 0 || a.vec2) {         // the shifting instances are only launched on aligned 2-sample loads
@@ -361,7 +384,7 @@ stft_kernel(const StftArgs a) {
         for (int j = 0; j < 8; ++j) raw[j] = tv2{(T)0, (T)0};
         if (nfr > 0) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) raw[j] = load_slot(f0, j);
+            for (int j = 0; j < 8; ++j) raw[j] = load_slot(xc, f0, j);
         }
     }
 
@@ -370,11 +393,28 @@ stft_kernel(const StftArgs a) {
     // emits vmcnt(0) at the top of every iteration, which would serialise the prefetch below.
     __builtin_amdgcn_s_waitcnt(0x0F70);               // vmcnt(0), other counters untouched
 
+    // The walk's run boundary.  Hop N/2: the last frame of a run is a variant of its own that requests the next run's first frame
+    // (above).  Hop N/4 has four phases, hence eight frame variants, and with them the instance does not fit three waves per SIMD
+    // (168 registers and 112-148 bytes of scratch per lane, split and packed rows alike): there the last frame re-requests its
+    // clamped slots like every instance, and the next run's first frame is loaded and drained (vmcnt(0)) between the runs.
+#ifndef FRT_WALK_PREFETCH_MIN_SHIFT
+#define FRT_WALK_PREFETCH_MIN_SHIFT 4
+#endif
+    constexpr bool WALK_PREFETCH = PERSIST && SHIFT >= FRT_WALK_PREFETCH_MIN_SHIFT;
     const int nloop = a.run;                          // uniform trip count keeps barriers aligned
     // one frame; `phase` = g mod NSETS as a compile-time constant; false = the run is finished
-    auto frame = [&](auto phase, const int g) -> bool {
+    // `last` (the walk only): the run's last frame, which requests the whole first frame of the wave's next run
+    auto frame = [&](auto phase, auto last, const int g) -> bool {
         constexpr int PH = decltype(phase)::value;
-        if (g >= nloop) return false;
+        constexpr bool LAST = decltype(last)::value;
+        static_assert(!LAST || WALK_PREFETCH, "");
+        // (the walk only calls frames that exist; the compare it cannot see through keeps the epilogue a block of its own, behind
+        // the transform, as in every other instance: folded into the transform's block the frame needs more registers than three waves allow)
+        if constexpr (!PERSIST) {
+            if (g >= nloop) return false;
+        }
+        // (the walk only calls frames that exist, but keeps the test and the way out below — there it ends the wave: with them the frame has
+        // the block structure of every other instance, and the compiler contracts the same multiply-adds — the same results bit for bit)
         const bool valid = g < nfr;
         if (!WAVE) {
             if (!__syncthreads_or(valid)) return false;      // whole block finished
@@ -440,17 +480,23 @@ stft_kernel(const StftArgs a) {
         // merge of "old value" and "loaded value", which the register allocator resolves with copies at the loop's
         // back-edge — the very moves this scheme removes.  The one redundant request per run re-reads slots this wave
         // fetched a frame ago.)
-        if constexpr (NSETS > 1) {
+        if constexpr (LAST) {
+            // the walk, last frame of a run: every slot has been read.  The next run starts in phase 0, where logical slot j is
+            // physical slot j.  (The wave's last run requests its own first frame again: the redundant request per WAVE.)
+#pragma unroll
+            for (int t = 0; t < 8; ++t) raw[t] = load_slot(xnext, fnext, t);
+        } else if constexpr (NSETS > 1) {
             int gn = g + 1 < nfr ? g + 1 : nfr - 1;
             if (gn < 0) gn = 0;
+            if constexpr (WALK_PREFETCH) gn = g + 1;    // not the last frame: no clamp
 #ifdef FRT_ABLATE
             if (a.ablate & 2) gn = 0;
 #endif
 #pragma unroll
-            for (int t = 0; t < NEW; ++t) raw[PH * NEW + t] = load_slot(f0 + gn, 8 - NEW + t);
+            for (int t = 0; t < NEW; ++t) raw[PH * NEW + t] = load_slot(xc, f0 + gn, 8 - NEW + t);
         } else if (g + 1 < nfr) {       // a hop that reloads the whole frame: the redundant request would be a whole frame
 #pragma unroll
-            for (int t = 0; t < 8; ++t) raw[t] = load_slot(f0 + g + 1, t);
+            for (int t = 0; t < 8; ++t) raw[t] = load_slot(xc, f0 + g + 1, t);
         }
         }
 
@@ -519,7 +565,10 @@ stft_kernel(const StftArgs a) {
         // The prefetched slots are waited for HERE, in front of this frame's stores: the vector-memory counter retires in
         // order, so a first use behind the stores (the next frame's window multiply) could only be guarded by vmcnt(0) —
         // the acknowledgement of every row store.  The empty asm makes the loaded values a use at this point.
-        if constexpr (!RING) {
+        if constexpr (LAST) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) asm volatile("" : "+v"(raw[t]));
+        } else if constexpr (!RING) {
 #pragma unroll
             for (int t = 0; t < NEW; ++t) asm volatile("" : "+v"(raw[PH * NEW + t]));
         }
@@ -715,20 +764,8 @@ stft_kernel(const StftArgs a) {
         }
         return true;
     };
-    for (int g = 0; g < nloop; g += NSETS) {
-        if (!frame(std::integral_constant<int, 0>{}, g)) break;
-        if constexpr (NSETS > 1) {
-            if (!frame(std::integral_constant<int, 1>{}, g + 1)) break;
-        }
-        if constexpr (NSETS > 2) {
-            if (!frame(std::integral_constant<int, 2>{}, g + 2)) break;
-            if constexpr (NSETS > 3) {
-                if (!frame(std::integral_constant<int, 3>{}, g + 3)) break;
-            }
-        }
-    }
-    if constexpr (NYQ_REG) {
-        // the run's Nyquist values: lane g holds frame g's (runs are at most 64 frames, stft_launch)
+    // the run's Nyquist values: lane g holds frame g's (runs are at most 64 frames, stft_launch)
+    auto flush_nyquist = [&]() {
         const long long at = chan * a.n_frames + f0 + i;
         uint32_t word = nyq_lo;                          // what a 4-byte plane receives: the value's bits, or the colour
         if constexpr (EIGHT_INST) {
@@ -750,6 +787,98 @@ stft_kernel(const StftArgs a) {
         if (i < nfr) {
             if (a.kind == FRT_STFT_IMAGE || sizeof(T) == 4) ((uint32_t*)a.out_nyq)[at] = word;
             else ((double*)a.out_nyq)[at] = __hiloint2double((int)nyq_hi, (int)nyq_lo);
+        }
+    };
+    using no_t = std::false_type;
+    if constexpr (!PERSIST) {
+        for (int g = 0; g < nloop; g += NSETS) {
+            if (!frame(std::integral_constant<int, 0>{}, no_t{}, g)) break;
+            if constexpr (NSETS > 1) {
+                if (!frame(std::integral_constant<int, 1>{}, no_t{}, g + 1)) break;
+            }
+            if constexpr (NSETS > 2) {
+                if (!frame(std::integral_constant<int, 2>{}, no_t{}, g + 2)) break;
+                if constexpr (NSETS > 3) {
+                    if (!frame(std::integral_constant<int, 3>{}, no_t{}, g + 3)) break;
+                }
+            }
+        }
+        if constexpr (NYQ_REG) flush_nyquist();
+    } else {
+        // ---- the walk ------------------------------------------------------------------------------------------------
+        // Every quantity of the run bookkeeping is wave-uniform and stays on the scalar unit; the step to the next lane group is
+        // an add and one conditional carry (the stride is split into channels and runs once per wave: no division per run).
+        using yes_t = std::true_type;
+        // The arguments the bookkeeping needs are re-read from the kernel-argument segment at every run (scalar loads that hit the
+        // scalar cache) through a pointer the compiler cannot see through: held in scalar registers across the frames they pushed
+        // the walk over the scalar register file, and the overflow went to vector registers.
+        typedef const StftArgs __attribute__((address_space(4))) * kernargs;
+        kernargs ka = (kernargs)__builtin_amdgcn_kernarg_segment_ptr();          // StftArgs is the kernel's only argument
+        const int stride = (int)gridDim.x * GPB;
+        const int dchan = stride / a.runs_per_channel, drun = stride - dchan * a.runs_per_channel;
+        for (;;) {
+            asm volatile("" : "+s"(ka));
+            const int gg_next = gg + stride;
+            const bool more = gg_next < ka->n_groups;
+            int chan_next = chan + dchan, run_next = run + drun;
+            if (run_next >= ka->runs_per_channel) {
+                run_next -= ka->runs_per_channel;
+                ++chan_next;
+            }
+            if (!more) {                                   // the wave's last run: its own first frame once more
+                chan_next = chan;
+                run_next = run;
+            }
+            chan_next = __builtin_amdgcn_readfirstlane(chan_next);
+            run_next = __builtin_amdgcn_readfirstlane(run_next);
+            xnext = (const TIN*)ka->x + chan_next * ka->x_stride;
+            fnext = ka->frame_base + (long long)run_next * ka->run;
+            // one run: nfr >= 1 frames, the last one through the variant that fetches the next run's first frame
+            if constexpr (!WALK_PREFETCH) {
+                for (int g = 0; g < nfr; g += NSETS) {
+                    if (!frame(std::integral_constant<int, 0>{}, no_t{}, g)) return;
+                    if (g + 1 >= nfr) break;
+                    if (!frame(std::integral_constant<int, 1>{}, no_t{}, g + 1)) return;
+                    if constexpr (NSETS > 2) {
+                        if (g + 2 >= nfr) break;
+                        if (!frame(std::integral_constant<int, 2>{}, no_t{}, g + 2)) return;
+                        if (g + 3 >= nfr) break;
+                        if (!frame(std::integral_constant<int, 3>{}, no_t{}, g + 3)) return;
+                    }
+                }
+            } else
+            for (int g = 0;; g += NSETS) {
+                if (g + 1 >= nfr) { if (!frame(std::integral_constant<int, 0>{}, yes_t{}, g)) return; break; }
+                if (!frame(std::integral_constant<int, 0>{}, no_t{}, g)) return;
+                if (g + 2 >= nfr) { if (!frame(std::integral_constant<int, 1>{}, yes_t{}, g + 1)) return; break; }
+                if (!frame(std::integral_constant<int, 1>{}, no_t{}, g + 1)) return;
+                if constexpr (NSETS > 2) {
+                    if (g + 3 >= nfr) { if (!frame(std::integral_constant<int, 2>{}, yes_t{}, g + 2)) return; break; }
+                    if (!frame(std::integral_constant<int, 2>{}, no_t{}, g + 2)) return;
+                    if (g + 4 >= nfr) { if (!frame(std::integral_constant<int, 3>{}, yes_t{}, g + 3)) return; break; }
+                    if (!frame(std::integral_constant<int, 3>{}, no_t{}, g + 3)) return;
+                }
+            }
+            if constexpr (NYQ_REG) {
+                flush_nyquist();
+                nyq_lo = 0;
+                nyq_hi = 0;
+            }
+            if (!more) break;
+            gg = gg_next;
+            chan = chan_next;
+            run = run_next;
+            f0 = fnext;
+            xc = xnext;
+            asm volatile("" : "+s"(ka));
+            outc = (T*)ka->out + chan * ka->out_cstride;
+            const long long left_next = ka->n_frames - f0;
+            nfr = left_next > ka->run ? ka->run : (int)left_next;
+            if constexpr (!WALK_PREFETCH) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) raw[j] = load_slot(xc, f0, j);
+                __builtin_amdgcn_s_waitcnt(0x0F70);       // vmcnt(0): the row stores of the run behind us as well
+            }
         }
     }
 }

@@ -64,6 +64,11 @@ class StftEngine:
     def set_run_length(self, frames: int):
         _lib.check(self._lib.frt_stft_set_run_length(self._h, int(frames)))
 
+    def set_persistent(self, mode: int = -1, blocks: int = 0):
+        """The walk of the float32 N = 1024 instances (frt_stft_set_persistent): mode -1 automatic, 0 never, 1 always;
+        blocks 0 = the device's resident workgroups, > 0 = this grid."""
+        _lib.check(self._lib.frt_stft_set_persistent(self._h, int(mode), int(blocks)))
+
     def frames_for(self, n_samples: int) -> int:
         return int(self._lib.frt_stft_frames_for(self._h, int(n_samples)))
 

@@ -130,6 +130,14 @@ int64_t frt_stft_frames_for(const frt_stft* h, int64_t T);
  * kernel instead of the radix-16 + wave-local one (A/B runs). */
 int frt_stft_set_run_length(frt_stft* h, int frames_per_run);
 
+/* The walk (float32, fft_size 1024, hop 512 or 256): a grid of as many workgroups as are resident on the device, whose
+ * wavefronts load their constants once and stride over runs of 16 frames.  Same values, bit for bit, as the launch of
+ * one run per lane group.  mode -1 = automatic (default: large batches with no run length set), 0 = never, 1 = always when
+ * such an instance exists (then a run length set with frt_stft_set_run_length is the walk's; in the other modes a set run
+ * length keeps the launch of one run per lane group).  blocks 0 = the resident count queried at create time, > 0 = this
+ * grid (tests). */
+int frt_stft_set_persistent(frt_stft* h, int mode, int blocks);
+
 /* ---- K2 / K4: octave filter bank with decimation, band energies -------------------------------
  * mode 0 replaces the exact IIR bank octave_filter_bank_decimation (friture/filter.py:86-118) built
  * on lfilter_float64_1D (friture/signal/lfilter.py:85-147) and decimate

@@ -2,6 +2,7 @@
 // 6.29 TB/s float4 copy of MI355X_MICROARCH.md.)
 //
 //   membench2 [MiB per buffer = 256] [buffer sets = 4]
+//   membench2 front [MiB per buffer = 256] [buffer sets = 4]      only the last section
 //
 // Sections, each line "tag ... GB/s" counts bytes read + bytes written:
 //   memcpy   hipMemcpyAsync device-to-device (the runtime's own blit kernel)
@@ -11,9 +12,15 @@
 //   write    write-only stream (fill)
 //   stft     the STFT kernel's shape (2 KB read + 2052-byte row written per wave and frame) at 12 or 32 waves per CU,
 //            prefetch depth 0 / 1 / 2 / 3 frames, 513- or 516-word rows
+//   front    the headline's present shape (split rows): four 8-byte loads per lane and frame (2 KB of new samples per wave, the whole
+//            4 KB frame at a run's start), eight non-temporal dword stores per lane and frame into 2048-byte rows, a Nyquist plane
+//            written a run at a time; three workgroups of four waves per CU.  Form (a): one run per wave, 76 constant dwords per lane
+//            re-read per run (L2-resident table), run lengths 16 / 8 / 4 / 2.  Form (b): a resident grid whose waves stride over the
+//            runs, constants read once per wave, the next run's first frame requested in the last frame of the run before.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #define HK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1);} } while (0)
 
@@ -157,6 +164,57 @@ __global__ void __launch_bounds__(256) stft_shape_k(const float* __restrict__ x,
     if (LDSB > 0 && acc == 12345.f) out[0] = pad[lane];
 }
 
+// the headline's present shape; see the header.  53248 bytes of LDS per block: three blocks per CU
+template <bool WALK>
+__global__ void __launch_bounds__(256) front_k(const float* __restrict__ x, float* __restrict__ rows, float* __restrict__ nyq,
+                                               const float* __restrict__ consts, int run, int nframes, int nruns) {
+    __shared__ float pad[53248 / 4];
+    if (run < 0) pad[threadIdx.x] = 1.f;                       // keeps the allocation
+    const int lane = threadIdx.x & 63;
+    const int wave0 = __builtin_amdgcn_readfirstlane((blockIdx.x * 256 + threadIdx.x) >> 6);
+    const int stride = WALK ? gridDim.x * 4 : nruns;           // form (a): one trip
+    if (wave0 >= nruns) return;
+    typedef float v2 __attribute__((ext_vector_type(2)));
+    auto slot = [&](long long f, int j) -> v2 { return *(const v2*)(x + f * 512 + 2 * (lane + 64 * j)); };
+    float acc = 0.f;
+    auto constants = [&]() {
+        float c = 0.f;
+#pragma unroll
+        for (int k = 0; k < 76; ++k) c += consts[lane + 64 * k];
+        return c * 1e-30f;
+    };
+    if (WALK) acc = constants();
+    v2 cur[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) cur[j] = slot((long long)wave0 * run, j);
+    for (int r = wave0; r < nruns; r += stride) {
+        const long long f0 = (long long)r * run;
+        int nfr = nframes - f0 > run ? run : (int)(nframes - f0);
+        if (!WALK) acc = constants();
+        const bool more = r + stride < nruns;
+        const long long fnext = more ? (long long)(r + stride) * run : f0;
+        float keep = 0.f;
+        for (int g = 0; g < nfr; ++g) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = cur[j].x + cur[j].y + acc;
+            if (g + 1 < nfr) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { cur[j] = cur[4 + j]; cur[4 + j] = slot(f0 + g + 1, 4 + j); }
+            } else if (WALK) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) cur[j] = slot(fnext, j);
+            }
+            float* rw = rows + (f0 + g) * 512;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) __builtin_nontemporal_store(v[j], rw + lane + 64 * j);
+            keep = lane == g ? v[0] : keep;
+        }
+        if (lane < nfr) nyq[f0 + lane] = keep;
+    }
+    if (acc == 12345.f) rows[0] = pad[lane];
+}
+
 static hipEvent_t e0, e1;
 static double time_ms(const std::function<void(int)>& launch, int warm, int iters) {
     for (int i = 0; i < warm; ++i) launch(i);
@@ -170,6 +228,8 @@ static double time_ms(const std::function<void(int)>& launch, int warm, int iter
 }
 
 int main(int argc, char** argv) {
+    const bool front_only = argc > 1 && !strcmp(argv[1], "front");
+    if (front_only) { --argc; ++argv; }
     const size_t mib = argc > 1 ? atoi(argv[1]) : 256;
     const int sets = argc > 2 ? atoi(argv[2]) : 4;
     const size_t bytes = mib << 20, n4 = bytes / 16;
@@ -187,6 +247,38 @@ int main(int argc, char** argv) {
     };
     // clock ramp
     time_ms([&](int i) { hipLaunchKernelGGL((copy_k<4, 0>), dim3(2048), dim3(256), 0, 0, X(i), O(i), (long long)(n4 / 1024)); }, 200, 2000);
+
+    // the headline's present shape: forms (a) and (b) at run lengths 16, 8, 4, 2
+    auto front = [&]() {
+        const int nfr = (int)(bytes / 2048) - 2;
+        const double mv = (double)nfr * 4100;
+        int cus = 0;
+        HK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
+        float* consts;
+        HK(hipMalloc(&consts, 76 * 64 * 4));
+        HK(hipMemset(consts, 0, 76 * 64 * 4));
+        char t[128];
+        printf("# front: %d frames per launch, %d buffer sets, resident grid %d workgroups; bytes counted: 4100 per frame\n", nfr, sets, 3 * cus);
+        for (int rep = 0; rep < 2; ++rep)
+        for (int run : {16, 8, 4, 2}) {
+            const int nruns = (nfr + run - 1) / run;
+            auto go = [&](bool walk, int i) {
+                float* o = (float*)O(i);
+                float* ny = o + bytes / 4;                      // behind the rows, inside the set's spare sixteenth
+                if (walk) hipLaunchKernelGGL((front_k<true>), dim3(3 * cus), dim3(256), 0, 0, (const float*)X(i), o, ny, consts, run, nfr, nruns);
+                else hipLaunchKernelGGL((front_k<false>), dim3((nruns + 3) / 4), dim3(256), 0, 0, (const float*)X(i), o, ny, consts, run, nfr, nruns);
+            };
+            snprintf(t, sizeof t, "front (a) one run per wave, run=%d", run);
+            report(t, time_ms([&](int i) { go(false, i); }, 50, 200), mv);
+            snprintf(t, sizeof t, "front (b) resident walk, run=%d", run);
+            report(t, time_ms([&](int i) { go(true, i); }, 50, 200), mv);
+        }
+        HK(hipFree(consts));
+    };
+    if (front_only) {
+        front();
+        return 0;
+    }
 
     report("memcpy d2d", time_ms([&](int i) { HK(hipMemcpyAsync(O(i), X(i), bytes, hipMemcpyDeviceToDevice, 0)); }, 20, 100), 2.0 * bytes);
 
@@ -230,5 +322,6 @@ int main(int argc, char** argv) {
     SHAPE(1, 36864, 513, 0, 0) SHAPE(1, 36864, 513, 1, 0) SHAPE(1, 36864, 513, 2, 0) SHAPE(1, 36864, 513, 3, 0)
     SHAPE(1, 36864, 513, 0, 1) SHAPE(1, 36864, 513, 1, 1) SHAPE(1, 36864, 513, 2, 1) SHAPE(1, 36864, 513, 3, 1)
     SHAPE(1, 0, 513, 0, 1) SHAPE(1, 0, 513, 1, 1) SHAPE(2, 36864, 513, 1, 1)
+    front();
     return 0;
 }

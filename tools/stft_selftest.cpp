@@ -3,7 +3,7 @@
 //   stft_selftest check            parity of every FFT size / hop class / output kind against a
 //                                  double-precision host FFT (not the oracle: a quick sanity gate
 //                                  that runs without Python)
-//   stft_selftest bench [N hop C log2T kind run iters precision split]
+//   stft_selftest bench [N hop C log2T kind run iters precision split persist blocks]
 //                                  HIP-event timing of frt_stft_run on device-resident input
 #include <hip/hip_runtime.h>
 
@@ -210,11 +210,12 @@ static int do_check() {
 }
 
 static int64_t nf_g;
-static int do_bench(int N, int hop, int C, int log2T, int kind, int run, int iters, int precision, int split) {
+static int do_bench(int N, int hop, int C, int log2T, int kind, int run, int iters, int precision, int split, int persist, int blocks) {
     const int64_t T = 1ll << log2T;
     frt_stft* h = nullptr;
     CK(frt_stft_create(&h, N, hop, C, precision));
     CK(frt_stft_set_run_length(h, run));
+    CK(frt_stft_set_persistent(h, persist, blocks));          // -1 automatic, 0 never, 1 the walk (then `run` is the walk's run length)
     std::vector<uint32_t> lut(256);
     for (int i = 0; i < 256; ++i) lut[i] = 0xFF000000u | (i * 0x010101);
     CK(frt_stft_set_epilogue(h, nullptr, -140.0, 0.0, lut.data()));
@@ -301,8 +302,8 @@ static int do_bench(int N, int hop, int C, int log2T, int kind, int run, int ite
     const double per = ms / iters * 1e-3;
     const double spectra = (double)C * F / per;
     const double bytes = (double)C * F * ((double)esz * hop + (double)oesz * nb);
-    printf("bench p%d N=%d hop=%d C=%d T=2^%d F=%lld kind=%d run=%d sets=%d %s: %.3f ms/launch  %.4e spectra/s  %.1f GB/s algorithmic (%.1f%% of 8 TB/s)  [isolated launch: %.3f ms]\n",
-           precision, N, hop, C, log2T, (long long)F, kind, run, sets, split ? "split" : "packed", per * 1e3, spectra, bytes / per * 1e-9, bytes / per / 8e12 * 100, iso_ms);
+    printf("bench p%d N=%d hop=%d C=%d T=2^%d F=%lld kind=%d run=%d persist=%d/%d sets=%d %s: %.4f ms/launch  %.4e spectra/s  %.1f GB/s algorithmic (%.1f%% of 8 TB/s)  [isolated launch: %.3f ms]\n",
+           precision, N, hop, C, log2T, (long long)F, kind, run, persist, blocks, sets, split ? "split" : "packed", per * 1e3, spectra, bytes / per * 1e-9, bytes / per / 8e12 * 100, iso_ms);
     frt_stft_destroy(h);
     HK(hipFree(dx_alloc));
     HK(hipFree(dout_alloc));
@@ -325,8 +326,10 @@ int main(int argc, char** argv) {
         int iters = argc > 8 ? atoi(argv[8]) : 20;
         int precision = argc > 9 ? atoi(argv[9]) : 32;
         int split = argc > 10 ? atoi(argv[10]) : 0;
-        return do_bench(N, hop, C, log2T, kind, run, iters, precision, split);
+        int persist = argc > 11 ? atoi(argv[11]) : -1;
+        int blocks = argc > 12 ? atoi(argv[12]) : 0;
+        return do_bench(N, hop, C, log2T, kind, run, iters, precision, split, persist, blocks);
     }
-    fprintf(stderr, "usage: stft_selftest check | bench [N hop C log2T kind run iters precision split]\n");
+    fprintf(stderr, "usage: stft_selftest check | bench [N hop C log2T kind run iters precision split persist blocks]\n");
     return 2;
 }
