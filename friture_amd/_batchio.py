@@ -5,7 +5,9 @@ in chunks (chunk_ends, checked_ends, frame_schedule); for the five chains over r
 checks (check_keep, check_samples; `dual` for two rows per stream), the hand-over to the null stream, the device copy of a
 carried state (carried) and the way back to numpy (to_host); for the two STFT chains, the sample front (RecordingFront).  The
 recording chains (Resampler, LoudnessBatch, TransferBatch, ConvolveBatch, DecayBatch, DeconvolveBatch, MtfBatch, SosBatch): the checks of the stream count and of scratch_bytes,
-the rows read in place (strided_rows) and the numpy / CUDA fork of run() (run_call)."""
+the rows read in place (strided_rows) and the numpy / CUDA fork of run() (run_call).  The chains over rows of samples (DecayBatch,
+MtfBatch; rowfront.h is their library side): the checks of fs and of the samples per row (check_fs, check_row_samples) and the
+per-row integers of onset / truncate / start / stop (row_integers)."""
 from __future__ import annotations
 
 import ctypes
@@ -117,6 +119,35 @@ def check_streams(S):
 def check_scratch_bytes(scratch_bytes):
     if isinstance(scratch_bytes, bool) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
         raise ValueError(f"scratch_bytes must be an integer >= 0, got {scratch_bytes!r}")
+
+
+def check_row_samples(T):
+    if not 1 <= T <= 1 << 24:
+        raise ValueError(f"expected 1 .. 2^24 samples per row, got {T}")
+
+
+def check_fs(fs):
+    if not (isinstance(fs, (int, float, np.integer, np.floating)) and math.isfinite(fs) and 100 <= fs <= 1e7):
+        raise ValueError(f"fs must lie in 100 .. 1e7, got {fs!r}")
+
+
+def row_integers(name, v, R, lo, hi, device=False):
+    """[R] int64 on the host from integers [R] or a scalar (a tensor comes to the host), every value within lo .. hi.
+    device=True: an int64 CUDA tensor passes as it is, unchecked: a bad value makes its row dead in the kernel."""
+    if device and getattr(v, "is_cuda", False):
+        import torch
+        if v.dtype != torch.int64 or tuple(v.shape) not in ((R,), ()) or v.numel() != R:
+            raise ValueError(f"{name} must be int64 [{R}], got {v.dtype} {tuple(v.shape)}")
+        return v.reshape(R).contiguous()
+    if hasattr(v, "cpu"):
+        v = v.cpu().numpy()
+    v = np.asarray(v)
+    if v.dtype.kind not in "iu" or v.shape not in ((R,), ()):
+        raise ValueError(f"{name} must be integers [{R}], got {v.dtype} {v.shape}")
+    v = np.ascontiguousarray(np.broadcast_to(v, (R,)), np.int64)
+    if v.size and (v.min() < lo or v.max() > hi):
+        raise ValueError(f"{name} must lie in {lo} .. {hi}, got {int(v.min())} .. {int(v.max())}")
+    return v
 
 
 def strided_rows(x, dual=False):

@@ -30,7 +30,7 @@
 #include <limits>
 
 #include "common.h"
-#include "hostio.h"
+#include "rowfront.h"
 
 using namespace frt;
 
@@ -40,7 +40,6 @@ constexpr int kPer = 8, kTile = 64 * kPer, kWaves = 4;       // samples per lane
 constexpr int kLdsPerWave = kTile + kTile / 8;               // a tile of doubles, one pad behind every 8
 constexpr int kParts = 21;                                   // 5 counts | 5 x (sum L, sum u L, sum L^2) | sum u e
 constexpr int kParams = 15, kIndices = 3;
-constexpr long long kMaxSamples = 1LL << 24;
 
 struct RowRec {
     long long t0, t1, peak;
@@ -70,26 +69,6 @@ struct Call {
 __device__ __forceinline__ double sample_at(const Call& p, long long row, long long t) {
     const long long at = row * p.row_stride + t;
     return p.dtype ? reinterpret_cast<const double*>(p.x)[at] : (double)reinterpret_cast<const float*>(p.x)[at];
-}
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <int G = 64>
-__device__ __forceinline__ double fold_sum(double v) {
-#pragma unroll
-    for (int m = G / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
-template <int G = 64>
-__device__ __forceinline__ double fold_max(double v) {
-#pragma unroll
-    for (int m = G / 2; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m));
-    return v;
 }
 
 template <int G>
@@ -450,10 +429,7 @@ extern "C" int frt_decay_create(frt_decay** out, double fs, int block, double on
 
 extern "C" void frt_decay_destroy(frt_decay* h) {
     if (!h) return;
-    (void)hipStreamSynchronize(h->stream);
-    for (DeviceBuffer* b : {&h->xin, &h->oin, &h->tin, &h->pout, &h->iout, &h->cout, &h->scratch}) b->release();
-    delete h;
-    free_retired_allocations(true);
+    destroy_handle(h, {&h->xin, &h->oin, &h->tin, &h->pout, &h->iout, &h->cout, &h->scratch});
 }
 
 extern "C" int frt_decay_set_stream(frt_decay* h, void* s) {
@@ -466,24 +442,16 @@ extern "C" int frt_decay_run(frt_decay* h, const void* x, int x_dtype, int rows,
                              int truncate_mode, const int64_t* truncation, int64_t curve_step, int64_t scratch_bytes, double* params,
                              int64_t* indices, double* curve) {
     FRT_REQUIRE(h, "frt_decay_run: null handle");
-    FRT_REQUIRE(x_dtype == 0 || x_dtype == 1, "frt_decay_run: x_dtype %d (0 float32, 1 float64)", x_dtype);
-    FRT_REQUIRE(rows >= 1 && rows <= 65535, "frt_decay_run: %d rows (1 .. 65535)", rows);
-    FRT_REQUIRE(n >= 1 && n <= kMaxSamples && x, "frt_decay_run: bad input (n %lld, 1 .. 2^24)", (long long)n);
-    FRT_REQUIRE(rows == 1 || row_stride >= n, "frt_decay_run: bad stride (n %lld, row stride %lld)", (long long)n, (long long)row_stride);
+    int rc;
+    if ((rc = require_rows("frt_decay_run", x, x_dtype, rows, n, row_stride, scratch_bytes))) return rc;
     FRT_REQUIRE(truncate_mode >= 0 && truncate_mode <= 2, "frt_decay_run: truncate_mode %d (0 none, 1 auto, 2 given)", truncate_mode);
     FRT_REQUIRE((truncate_mode == 2) == (truncation != nullptr), "frt_decay_run: truncation is given with truncate_mode 2 and only then");
     FRT_REQUIRE(curve_step >= 0 && (curve_step > 0) == (curve != nullptr), "frt_decay_run: curve_step %lld %s a curve",
                 (long long)curve_step, curve ? "with" : "without");
-    FRT_REQUIRE(scratch_bytes >= 0, "frt_decay_run: scratch_bytes %lld", (long long)scratch_bytes);
     FRT_REQUIRE(params && indices, "frt_decay_run: null output");
-    static_assert(sizeof(long long) == sizeof(int64_t), "int64_t is long long here");
     const long long T = n, W = h->W, R = rows;
-    if (onset && !is_device_pointer(onset))
-        for (long long r = 0; r < R; ++r)
-            FRT_REQUIRE(onset[r] >= 0 && onset[r] < T, "frt_decay_run: onset[%lld] = %lld (0 .. n - 1)", r, (long long)onset[r]);
-    if (truncation && !is_device_pointer(truncation))
-        for (long long r = 0; r < R; ++r)
-            FRT_REQUIRE(truncation[r] >= 1 && truncation[r] <= T, "frt_decay_run: truncation[%lld] = %lld (1 .. n)", r, (long long)truncation[r]);
+    if ((rc = require_row_integers("frt_decay_run", "onset", onset, R, 0, T - 1, "0 .. n - 1"))) return rc;
+    if ((rc = require_row_integers("frt_decay_run", "truncation", truncation, R, 1, T, "1 .. n"))) return rc;
 
     Call p{};
     p.x = x;
@@ -507,7 +475,6 @@ extern "C" int frt_decay_run(frt_decay* h, const void* x, int x_dtype, int rows,
     p.step = curve_step;
     p.nc = curve_step ? (T + curve_step - 1) / curve_step : 0;
 
-    int rc;
     HostIO io(h->stream);
     const size_t xsize = x_dtype ? sizeof(double) : sizeof(float);
     const long long* on = reinterpret_cast<const long long*>(onset);
@@ -520,11 +487,10 @@ extern "C" int frt_decay_run(frt_decay* h, const void* x, int x_dtype, int rows,
     if ((rc = io.out(h->iout, ix, (size_t)R * kIndices))) return rc;
     if ((rc = io.out(h->cout, curve, (size_t)R * p.nc))) return rc;
 
-    // row slabs: the scratch of one launch stays within scratch_bytes, at least one row per launch
     const long long doubles = 2 * p.nblk + (2 + kParts) * p.ntile;
     const long long per_row = doubles * (long long)sizeof(double) + (long long)sizeof(RowRec);
-    const long long slab = std::min(R, std::max(1LL, scratch_bytes / per_row));
-    if ((rc = h->scratch.reserve((size_t)(slab * per_row)))) return rc;
+    long long slab;
+    if ((rc = reserve_slab(h->scratch, R, scratch_bytes, per_row, slab))) return rc;
     double* at = h->scratch.as<double>();
     p.q = at;
     p.m = (at += slab * p.nblk);
@@ -535,13 +501,9 @@ extern "C" int frt_decay_run(frt_decay* h, const void* x, int x_dtype, int rows,
     const char* x0 = reinterpret_cast<const char*>(p.x);
     const int G = W >= 64 ? 64 : 8;
     const unsigned front_groups = (unsigned)((p.nblk + kWaves * (64 / G) - 1) / (kWaves * (64 / G)));
-    // dk_totals, dk_scan: the workgroups of a row loop over its live tiles, so that a short decay in a long row costs no launch
-    // of idle workgroups; enough of them per row to fill the device when the rows are few
-    const long long all_groups = (p.ntile + kWaves - 1) / kWaves;
     for (long long r0 = 0; r0 < R; r0 += slab) {
         const unsigned nr = (unsigned)std::min(slab, R - r0);
-        // tests/test_decay_edges_gpu.py (the tile loops' second trip) derives its shapes from this formula: change both together
-        const unsigned tile_groups = (unsigned)std::min(all_groups, std::max(16LL, (8192 + nr - 1) / (long long)nr));
+        const unsigned groups = tile_groups(p.ntile, nr, kWaves);        // dk_totals, dk_scan: the workgroups of a row loop over its live tiles
         Call c = p;
         c.x = x0 + (size_t)r0 * (size_t)p.row_stride * xsize;
         c.onset = on ? on + r0 : nullptr;
@@ -554,7 +516,7 @@ extern "C" int frt_decay_run(frt_decay* h, const void* x, int x_dtype, int rows,
         FRT_HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(dk_plan, dim3(nr), dim3(64), 0, h->stream, c);
         FRT_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(dk_totals, dim3(tile_groups, nr), dim3(64 * kWaves), 0, h->stream, c);
+        hipLaunchKernelGGL(dk_totals, dim3(groups, nr), dim3(64 * kWaves), 0, h->stream, c);
         FRT_HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(dk_offsets, dim3(nr), dim3(64), 0, h->stream, c);
         FRT_HIP_CHECK(hipGetLastError());
@@ -562,7 +524,7 @@ extern "C" int frt_decay_run(frt_decay* h, const void* x, int x_dtype, int rows,
             hipLaunchKernelGGL(dk_curve_tail, dim3((unsigned)((p.nc + 255) / 256), nr), dim3(256), 0, h->stream, c);
             FRT_HIP_CHECK(hipGetLastError());
         }
-        hipLaunchKernelGGL(dk_scan, dim3(tile_groups, nr), dim3(64 * kWaves), 0, h->stream, c);
+        hipLaunchKernelGGL(dk_scan, dim3(groups, nr), dim3(64 * kWaves), 0, h->stream, c);
         FRT_HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(dk_finish, dim3(nr), dim3(64), 0, h->stream, c);
         FRT_HIP_CHECK(hipGetLastError());

@@ -24,7 +24,7 @@
 #include <limits>
 
 #include "common.h"
-#include "hostio.h"
+#include "rowfront.h"
 
 using namespace frt;
 
@@ -32,7 +32,6 @@ namespace {
 
 constexpr int kPer = 64, kTile = 64 * kPer, kWaves = 4, kFinishWaves = 8;
 constexpr int kMaxFreqs = 16, kBands = 7;
-constexpr long long kMaxSamples = 1LL << 24;
 constexpr long long kMaxTiles = kMaxSamples / kTile;
 
 struct Call {
@@ -54,18 +53,6 @@ __device__ __forceinline__ void load_squares(const T* __restrict__ x, long long 
         const double v = (double)x[min(max(t, lo), hi - 1)];
         e[q] = (t >= lo && t < hi) ? v * v : 0.0;
     }
-}
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ double fold_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
 }
 
 // the interval of a row; false: the row is dead (only device arrays can carry a bad one this far)
@@ -265,10 +252,7 @@ extern "C" int frt_mtf_create(frt_mtf** out, double fs, const double* freqs, int
 
 extern "C" void frt_mtf_destroy(frt_mtf* h) {
     if (!h) return;
-    (void)hipStreamSynchronize(h->stream);
-    for (DeviceBuffer* b : {&h->tables, &h->xin, &h->sin, &h->pin, &h->mout, &h->eout, &h->scratch}) b->release();
-    delete h;
-    free_retired_allocations(true);
+    destroy_handle(h, {&h->tables, &h->xin, &h->sin, &h->pin, &h->mout, &h->eout, &h->scratch});
 }
 
 extern "C" int frt_mtf_set_stream(frt_mtf* h, void* s) {
@@ -280,26 +264,21 @@ extern "C" int frt_mtf_set_stream(frt_mtf* h, void* s) {
 extern "C" int frt_mtf_run(frt_mtf* h, const void* x, int x_dtype, int rows, int64_t n, int64_t row_stride, const int64_t* start,
                            const int64_t* stop, int64_t scratch_bytes, double* m, double* energy) {
     FRT_REQUIRE(h, "frt_mtf_run: null handle");
-    FRT_REQUIRE(x_dtype == 0 || x_dtype == 1, "frt_mtf_run: x_dtype %d (0 float32, 1 float64)", x_dtype);
-    FRT_REQUIRE(rows >= 1 && rows <= 65535, "frt_mtf_run: %d rows (1 .. 65535)", rows);
-    FRT_REQUIRE(n >= 1 && n <= kMaxSamples && x, "frt_mtf_run: bad input (n %lld, 1 .. 2^24)", (long long)n);
-    FRT_REQUIRE(rows == 1 || row_stride >= n, "frt_mtf_run: bad stride (n %lld, row stride %lld)", (long long)n, (long long)row_stride);
-    FRT_REQUIRE(scratch_bytes >= 0, "frt_mtf_run: scratch_bytes %lld", (long long)scratch_bytes);
+    int rc;
+    if ((rc = require_rows("frt_mtf_run", x, x_dtype, rows, n, row_stride, scratch_bytes))) return rc;
     FRT_REQUIRE(m && energy, "frt_mtf_run: null output");
-    static_assert(sizeof(long long) == sizeof(int64_t), "int64_t is long long here");
     const long long T = n, R = rows;
-    const bool host_start = start && !is_device_pointer(start), host_stop = stop && !is_device_pointer(stop);
-    for (long long r = 0; r < R; ++r) {
-        const long long lo = host_start ? start[r] : 0, hi = host_stop ? stop[r] : T;
-        FRT_REQUIRE(!host_start || (lo >= 0 && lo < T), "frt_mtf_run: start[%lld] = %lld (0 .. n - 1)", r, lo);
-        FRT_REQUIRE(!host_stop || (hi >= 1 && hi <= T), "frt_mtf_run: stop[%lld] = %lld (1 .. n)", r, hi);
-        FRT_REQUIRE((start && !host_start) || (stop && !host_stop) || lo < hi, "frt_mtf_run: start[%lld] = %lld is not below stop = %lld", r, lo, hi);
-    }
+    if ((rc = require_row_integers("frt_mtf_run", "start", start, R, 0, T - 1, "0 .. n - 1"))) return rc;
+    if ((rc = require_row_integers("frt_mtf_run", "stop", stop, R, 1, T, "1 .. n"))) return rc;
+    if ((start || stop) && !is_device_pointer(start) && !is_device_pointer(stop))        // the host sees the intervals whole
+        for (long long r = 0; r < R; ++r) {
+            const long long lo = start ? start[r] : 0, hi = stop ? stop[r] : T;
+            FRT_REQUIRE(lo < hi, "frt_mtf_run: start[%lld] = %lld is not below stop = %lld", r, lo, hi);
+        }
 
     const int nf = h->nf, np = 1 + 2 * nf;
     if (!h->uploaded) {
-        int rc = h->tables.reserve(h->host.size() * sizeof(double2));
-        if (rc) return rc;
+        if ((rc = h->tables.reserve(h->host.size() * sizeof(double2)))) return rc;
         FRT_HIP_CHECK(hipMemcpyAsync(h->tables.ptr, h->host.data(), h->host.size() * sizeof(double2), hipMemcpyHostToDevice, h->stream));
         h->uploaded = true;
     }
@@ -312,7 +291,6 @@ extern "C" int frt_mtf_run(frt_mtf* h, const void* x, int x_dtype, int rows, int
     p.ntile = (T + kTile - 1) / kTile;
     const double2 *step = h->tables.as<const double2>(), *lanes = step + nf * kPer, *coarse = lanes + nf * 64;
 
-    int rc;
     HostIO io(h->stream);
     const size_t xsize = x_dtype ? sizeof(double) : sizeof(float);
     const long long* lo = reinterpret_cast<const long long*>(start);
@@ -323,25 +301,19 @@ extern "C" int frt_mtf_run(frt_mtf* h, const void* x, int x_dtype, int rows, int
     if ((rc = io.out(h->mout, m, (size_t)R * nf))) return rc;
     if ((rc = io.out(h->eout, energy, (size_t)R))) return rc;
 
-    // row slabs: the scratch of one launch stays within scratch_bytes, at least one row per launch
-    const long long per_row = p.ntile * np * (long long)sizeof(double);
-    const long long slab = std::min(R, std::max(1LL, scratch_bytes / per_row));
-    if ((rc = h->scratch.reserve((size_t)(slab * per_row)))) return rc;
+    long long slab;
+    if ((rc = reserve_slab(h->scratch, R, scratch_bytes, p.ntile * np * (long long)sizeof(double), slab))) return rc;
     p.part = h->scratch.as<double>();
     const char* x0 = reinterpret_cast<const char*>(p.x);
-    // the workgroups of a row loop over its live tiles; enough of them per row to fill the device when the rows are few
-    const long long all_groups = (p.ntile + kWaves - 1) / kWaves;
     for (long long r0 = 0; r0 < R; r0 += slab) {
         const unsigned nr = (unsigned)std::min(slab, R - r0);
-        // tests/test_sti_edges_gpu.py (the tile loop's second trip) derives its shapes from this formula: change both together
-        const unsigned tile_groups = (unsigned)std::min(all_groups, std::max(16LL, (8192 + nr - 1) / (long long)nr));
         Call c = p;
         c.x = x0 + (size_t)r0 * (size_t)p.row_stride * xsize;
         c.start = lo ? lo + r0 : nullptr;
         c.stop = hi ? hi + r0 : nullptr;
         c.m = m + r0 * nf;
         c.energy = energy + r0;
-        hipLaunchKernelGGL(mtf_tiles, dim3(tile_groups, nr), dim3(64 * kWaves), 0, h->stream, c, step, lanes, coarse);
+        hipLaunchKernelGGL(mtf_tiles, dim3(tile_groups(p.ntile, nr, kWaves), nr), dim3(64 * kWaves), 0, h->stream, c, step, lanes, coarse);
         FRT_HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(mtf_finish, dim3(nr), dim3(64 * kFinishWaves), 0, h->stream, c);
         FRT_HIP_CHECK(hipGetLastError());

@@ -29,7 +29,7 @@
 #include <vector>
 
 #include "common.h"
-#include "hostio.h"
+#include "rowfront.h"
 
 using namespace frt;
 
@@ -41,7 +41,6 @@ constexpr int kWaves = 4, kRun = 64;                 // wavefronts per cells wor
 constexpr int kStateVecs = 5;                        // z (running), p (partial zero-state run), s (S_c), q (partial Q), u (U_r)
 constexpr int kDefaultCell = 256;                    // measured: tools/bench_sos.py --cells (DESIGN X6)
 constexpr int kAhead = 16;                           // runs whose Q the level-two walk holds in registers ahead of its steps
-constexpr long long kMaxSamples = 1LL << 24;
 
 struct Call {
     const void* x;              // [rows][x_stride]
@@ -58,12 +57,6 @@ struct Call {
     double* st_out;
     double *E, *St, *Q, *U, *Z; // scratch: [orows][2K][ncp] x 2, [orows][2K][nr] x 2, [orows][2K]
 };
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <int K, bool OUT, bool FAN>
 __global__ __launch_bounds__(64 * kWaves) void sos_cells_kernel(const Call p) {
@@ -385,10 +378,7 @@ extern "C" int frt_sos_create(frt_sos** out, const double* sos, int filters, int
 
 extern "C" void frt_sos_destroy(frt_sos* h) {
     if (!h) return;
-    (void)hipStreamSynchronize(h->stream);
-    for (DeviceBuffer* b : {&h->coef, &h->M, &h->M64, &h->xin, &h->sin, &h->sout, &h->yout, &h->scratch}) b->release();
-    delete h;
-    free_retired_allocations(true);
+    destroy_handle(h, {&h->coef, &h->M, &h->M64, &h->xin, &h->sin, &h->sout, &h->yout, &h->scratch});
 }
 
 extern "C" int frt_sos_set_stream(frt_sos* h, void* s) {
@@ -429,16 +419,13 @@ int launch_slab(const Call& c, unsigned rows, long long orows, hipStream_t strea
 extern "C" int frt_sos_run(frt_sos* h, const void* x, int x_dtype, int rows, int64_t n, int64_t row_stride, int fan, int reverse,
                            int64_t n_before, const double* state_in, double* state_out, int64_t scratch_bytes, void* y, int y_dtype) {
     FRT_REQUIRE(h, "frt_sos_run: null handle");
-    FRT_REQUIRE(x_dtype == 0 || x_dtype == 1, "frt_sos_run: x_dtype %d (0 float32, 1 float64)", x_dtype);
+    int rc;
+    if ((rc = require_rows("frt_sos_run", x, x_dtype, rows, n, row_stride, scratch_bytes))) return rc;
     FRT_REQUIRE(y_dtype == 0 || y_dtype == 1, "frt_sos_run: y_dtype %d (0 float32, 1 float64)", y_dtype);
-    FRT_REQUIRE(rows >= 1 && rows <= 65535, "frt_sos_run: %d rows (1 .. 65535)", rows);
-    FRT_REQUIRE(n >= 1 && n <= kMaxSamples && x, "frt_sos_run: bad input (n %lld, 1 .. 2^24)", (long long)n);
-    FRT_REQUIRE(rows == 1 || row_stride >= n, "frt_sos_run: bad stride (n %lld, row stride %lld)", (long long)n, (long long)row_stride);
     FRT_REQUIRE((fan == 0 || fan == 1) && (reverse == 0 || reverse == 1), "frt_sos_run: fan %d, reverse %d (0 or 1)", fan, reverse);
     FRT_REQUIRE(n_before >= 0 && n_before <= (1LL << 60), "frt_sos_run: n_before %lld (0 .. 2^60)", (long long)n_before);
     FRT_REQUIRE(!reverse || (!state_in && !state_out && n_before == 0), "frt_sos_run: reverse runs whole rows from the zero state: no state");
     FRT_REQUIRE(state_in || n_before == 0, "frt_sos_run: n_before %lld without a state", (long long)n_before);
-    FRT_REQUIRE(scratch_bytes >= 0, "frt_sos_run: scratch_bytes %lld", (long long)scratch_bytes);
     FRT_REQUIRE(y, "frt_sos_run: null output");
     const Design& d = h->d;
     const int NS = 2 * d.K, opr = fan ? d.F : 1;
@@ -468,7 +455,6 @@ extern "C" int frt_sos_run(frt_sos* h, const void* x, int x_dtype, int rows, int
     p.st_in = state_in;
     p.st_out = state_out;
 
-    int rc;
     HostIO io(h->stream);
     const size_t xsize = x_dtype ? sizeof(double) : sizeof(float), ysize = y_dtype ? sizeof(double) : sizeof(float);
     long long y_ld = T;
@@ -477,11 +463,9 @@ extern "C" int frt_sos_run(frt_sos* h, const void* x, int x_dtype, int rows, int
     if ((rc = io.out_rows(h->yout, p.y, y_ld, (size_t)OR, T, ysize))) return rc;
     if ((rc = io.out(h->sout, p.st_out, (size_t)OR * kStateVecs * NS))) return rc;
 
-    // row slabs: the scratch of one launch stays within scratch_bytes, at least one row per launch
     const long long per_orow = (long long)NS * (2LL * p.ncp + 2LL * p.nr + 1);
-    const long long per_row = per_orow * opr * (long long)sizeof(double);
-    const long long slab = std::min(R, std::max(1LL, scratch_bytes / per_row));
-    if ((rc = h->scratch.reserve((size_t)(slab * per_row)))) return rc;
+    long long slab;
+    if ((rc = reserve_slab(h->scratch, R, scratch_bytes, per_orow * opr * (long long)sizeof(double), slab))) return rc;
     const long long so = slab * opr;
     double* at = h->scratch.as<double>();
     p.E = at;

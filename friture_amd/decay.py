@@ -30,10 +30,10 @@ order of the sums: X3).  Out of scope: a carried state (a decay is integrated fr
 Lundeby's iteration, the tail-compensation term, noise subtraction, sample rates handled in any way other than the fs argument
 (IIR band filters: room_acoustics(filters="butterworth"), X6, friture_amd/sosfilter.py).  There is no CPU fallback: run() goes to the HIP library.
 
-The band front (band_edges, band_filter, room_acoustics) is composition: a Kaiser-windowed linear-phase FIR per band, designed
-on the host, applied by ConvolveBatch, its delay cut off by a strided view that DecayBatch reads in place; or, with
-filters="butterworth" / "butterworth-reversed", Butterworth band-passes on the IEC 61260-1 base-ten band edges run as one bank
-by SosBatch."""
+The band front (band_edges, band_filter, band_front, band_axis) is composition, shared by room_acoustics and
+sti.speech_transmission: a Kaiser-windowed linear-phase FIR per band, designed on the host, applied by ConvolveBatch, its delay
+cut off by a strided view that the consumer reads in place; or, with filters="butterworth" / "butterworth-reversed", Butterworth
+band-passes on the IEC 61260-1 base-ten band edges run as one bank by SosBatch."""
 from __future__ import annotations
 
 import ctypes
@@ -52,19 +52,6 @@ DecayResult = namedtuple("DecayResult", "edt t10 t20 t30 r2 c50 c80 d50 ts level
 RoomResult = namedtuple("RoomResult", "centres broadband bands")
 
 
-def _row_integers(name, v, R, lo, hi):
-    """[R] int64 on the host, every value within lo .. hi."""
-    if hasattr(v, "cpu"):
-        v = v.cpu().numpy()
-    v = np.asarray(v)
-    if v.dtype.kind not in "iu" or v.shape not in ((R,), ()):
-        raise ValueError(f"{name} must be integers [{R}], got {v.dtype} {v.shape}")
-    v = np.ascontiguousarray(np.broadcast_to(v, (R,)), np.int64)
-    if v.size and (v.min() < lo or v.max() > hi):
-        raise ValueError(f"{name} must lie in {lo} .. {hi}, got {int(v.min())} .. {int(v.max())}")
-    return v
-
-
 class DecayBatch:
     """DecayBatch(fs=48000, block=480, onset_db=-20.0, noise_tail=0.1, margin_db=10.0).run(ir, onset=None, truncate="auto",
     keep=("params",), curve_step=48, scratch_bytes=1 << 28) -> DecayResult.  ir: [R, T] or [T], float32 or float64, numpy array or
@@ -76,8 +63,7 @@ class DecayBatch:
     def __init__(self, fs=48000, block=480, onset_db=-20.0, noise_tail=0.1, margin_db=10.0):
         if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or not MIN_BLOCK <= block <= MAX_BLOCK:
             raise ValueError(f"block must be an integer in {MIN_BLOCK} .. {MAX_BLOCK}, got {block!r}")
-        if not (math.isfinite(fs) and 100 <= fs <= 1e7):
-            raise ValueError(f"fs must lie in 100 .. 1e7, got {fs!r}")
+        _batchio.check_fs(fs)
         if not (math.isfinite(onset_db) and onset_db <= 0):
             raise ValueError(f"onset_db must be at most 0, got {onset_db!r}")
         if not 0 < noise_tail <= 1:
@@ -97,8 +83,7 @@ class DecayBatch:
         x, is_np, squeeze, _ = _batchio.check_samples("DecayBatch", ir, None)
         R, T = x.shape
         _batchio.check_streams(R)
-        if not 1 <= T <= MAX_SAMPLES:
-            raise ValueError(f"expected 1 .. 2^24 samples per row, got {T}")
+        _batchio.check_row_samples(T)
         _batchio.check_scratch_bytes(scratch_bytes)
         keep = tuple(keep) if isinstance(keep, (list, tuple)) else keep
         _batchio.check_keep(keep, ("params",), ("params", "curve"))
@@ -107,7 +92,7 @@ class DecayBatch:
             if isinstance(curve_step, bool) or not isinstance(curve_step, (int, np.integer)) or not 1 <= curve_step <= MAX_SAMPLES:
                 raise ValueError(f"curve_step must be an integer in 1 .. 2^24, got {curve_step!r}")
             step = int(curve_step)
-        t0 = None if onset is None else _row_integers("onset", onset, R, 0, T - 1)
+        t0 = None if onset is None else _batchio.row_integers("onset", onset, R, 0, T - 1)
         if truncate is None:
             mode, t1 = 0, None
         elif isinstance(truncate, str):
@@ -115,7 +100,7 @@ class DecayBatch:
                 raise ValueError(f"truncate={truncate!r} ('auto', None or integers [{R}])")
             mode, t1 = 1, None
         else:
-            mode, t1 = 2, _row_integers("truncate", truncate, R, 1, T)
+            mode, t1 = 2, _batchio.row_integers("truncate", truncate, R, 1, T)
             if t0 is not None and np.any(t1 <= t0):
                 raise ValueError("truncate must lie behind the onset in every row")
         h = self._handle()
@@ -183,14 +168,47 @@ def band_filter(f_lo, f_hi, fs=48000, attenuation_db=60.0, transition=0.25):
     return (2 * hi * np.sinc(2 * hi * n) - 2 * lo * np.sinc(2 * lo * n)) * np.kaiser(2 * M + 1, beta)
 
 
-def _per_band(v, B):
-    """A per-response vector [S] (or a scalar) with every entry B times in a row: [S B], numpy or tensor as it came."""
-    if hasattr(v, "repeat_interleave"):
-        return v.reshape(-1).repeat_interleave(B)
-    return np.repeat(np.asarray(v).reshape(-1), B)
-
-
 FILTERS = ("fir", "butterworth", "butterworth-reversed")
+
+
+def check_filters(filters):
+    if filters not in FILTERS:
+        raise ValueError(f"filters={filters!r} ({', '.join(repr(f) for f in FILTERS)})")
+
+
+def band_front(ir, edges, fs, filters, order):
+    """The responses ir [S, T] or [T] through the band-passes on `edges`, as (rows, spread) pairs that a consumer runs on as
+    they come; spread(v) makes a per-response vector v [S] fit `rows`.  filters="fir": one pair per band, rows =
+    ConvolveBatch(band_filter(..)).run(ir).y[..., M : M + T], the delay cut off by a view, and v as it is.  Otherwise: one
+    pair, the [S B, T] view of one bank run of SosBatch over the Butterworth band-passes of `order` (backwards in time for
+    "butterworth-reversed") in float64, and every entry of v (or a scalar) once per band: [S B].  A band is filtered only
+    when its pair is asked for; band_axis is the way back."""
+    T = ir.shape[-1]
+    if filters == "fir":
+        for f_lo, f_hi in edges:
+            h = band_filter(f_lo, f_hi, fs)
+            M = (len(h) - 1) // 2
+            yield convolve.ConvolveBatch(h).run(ir).y[..., M:M + T], lambda v: v
+        return
+    from . import sosfilter
+    sos = np.stack([sosfilter.butter_band_sos(f_lo, f_hi, fs, order) for f_lo, f_hi in edges])
+    y = sosfilter.SosBatch(sos).run(ir, fan=True, reverse=filters == "butterworth-reversed", dtype="float64").y
+
+    def spread(v):                                                   # numpy or tensor as it came
+        return v.reshape(-1).repeat_interleave(len(edges)) if hasattr(v, "repeat_interleave") else np.repeat(np.asarray(v).reshape(-1), len(edges))
+    yield y.reshape(-1, T), spread
+
+
+def band_axis(ir, B, filters, values):
+    """One result per pair of band_front (per row of its rows, with any axes behind) as one array with a band axis behind ir's
+    response axis: [S, B, ..], and [B, ..] for ir [T]."""
+    lead = tuple(ir.shape[:-1])
+    if filters != "fir":
+        return values[0].reshape(lead + (B,) + tuple(values[0].shape[1:]))
+    if isinstance(ir, np.ndarray):
+        return np.stack(values, len(lead))
+    import torch
+    return torch.stack(values, len(lead))
 
 
 def room_acoustics(ir, bands="octave", fs=48000, filters="fir", order=3, **decay_settings):
@@ -202,38 +220,18 @@ def room_acoustics(ir, bands="octave", fs=48000, filters="fir", order=3, **decay
     DecayBatch.run with the broadband onsets repeated: no loop over the bands and no delay to cut.  "butterworth-reversed" runs
     the bank backwards in time (ISO 3382: a band's own ringing then lies in front of the decay, not on it).  decay_settings:
     DecayBatch's parameters, and truncate / scratch_bytes of its run()."""
-    if filters not in FILTERS:
-        raise ValueError(f"filters={filters!r} ({', '.join(repr(f) for f in FILTERS)})")
+    check_filters(filters)
     run_settings = {k: decay_settings.pop(k) for k in ("truncate", "scratch_bytes") if k in decay_settings}
     centres, edges = band_edges(bands)
     db = DecayBatch(fs=fs, **decay_settings)
     broadband = db.run(ir, **run_settings)
-    T = ir.shape[-1]
-    if filters != "fir":
-        from . import sosfilter
-        B = len(centres)
-        sos = np.stack([sosfilter.butter_band_sos(f_lo, f_hi, fs, order) for f_lo, f_hi in edges])
-        y = sosfilter.SosBatch(sos).run(ir, fan=True, reverse=filters == "butterworth-reversed", dtype="float64").y
-        if not (run_settings.get("truncate") is None or isinstance(run_settings["truncate"], str)):
-            run_settings["truncate"] = _per_band(run_settings["truncate"], B)
-        res = db.run(y.reshape(-1, T), onset=_per_band(broadband.onset, B), **run_settings)
-        lead = tuple(ir.shape[:-1]) + (B,)
-        fields = [None if v is None else v.reshape(lead + tuple(v.shape[1:])) for v in res]
-        return RoomResult(centres, broadband, DecayResult(*fields))
-    per_band = []
-    for f_lo, f_hi in edges:
-        h = band_filter(f_lo, f_hi, fs)
-        M = (len(h) - 1) // 2
-        y = convolve.ConvolveBatch(h).run(ir).y
-        per_band.append(db.run(y[..., M:M + T], onset=broadband.onset, **run_settings))
-    axis = 1 if ir.ndim == 2 else 0
-    if isinstance(ir, np.ndarray):
-        def stack(v):
-            return np.stack(v, axis)
-    else:
-        import torch
-
-        def stack(v):
-            return torch.stack(v, axis)
-    fields = [None if name == "curve" else stack([getattr(r, name) for r in per_band]) for name in DecayResult._fields]
+    given = not (run_settings.get("truncate") is None or isinstance(run_settings["truncate"], str))       # truncations [S]
+    results = []
+    for rows, spread in band_front(ir, edges, fs, filters, order):
+        if given:
+            run_settings["truncate"] = spread(run_settings["truncate"])
+        results.append(db.run(rows, onset=spread(broadband.onset), **run_settings))
+    fields = [None if v[0] is None else band_axis(ir, len(centres), filters, v) for v in zip(*results)]
     return RoomResult(centres, broadband, DecayResult(*fields))
+
+

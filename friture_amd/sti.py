@@ -37,7 +37,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _batchio, _lib, convolve, decay
+from . import _batchio, _lib, decay
 
 TILE = 4096                                 # samples per tile of the sums (frt_mtf_tile)
 MAX_SAMPLES = 1 << 24
@@ -67,16 +67,6 @@ def octave_bands():
     return [(1000.0 * G ** (k - 0.5), 1000.0 * G ** (k + 0.5)) for k in range(-3, 4)]
 
 
-def _row_integers(name, v, R, lo, hi):
-    """[R] int64: a CUDA tensor passes as it is (a bad value makes its row dead), a host array is checked against lo .. hi."""
-    if hasattr(v, "is_cuda") and v.is_cuda:
-        import torch
-        if v.dtype != torch.int64 or tuple(v.shape) not in ((R,), ()) or v.numel() != R:
-            raise ValueError(f"{name} must be int64 [{R}], got {v.dtype} {tuple(v.shape)}")
-        return v.reshape(R).contiguous()
-    return decay._row_integers(name, v, R, lo, hi)
-
-
 class MtfBatch:
     """MtfBatch(freqs=MOD_FREQS, fs=48000).run(x, start=None, stop=None, scratch_bytes=1 << 28) -> MtfResult(m, energy).  x: [R, T]
     or [T], float32 or float64, numpy array or CUDA tensor (strided row views are read in place).  The results are of x's kind:
@@ -85,8 +75,7 @@ class MtfBatch:
     scratch_bytes; the result has the same bits at any slab size."""
 
     def __init__(self, freqs=MOD_FREQS, fs=48000):
-        if not (isinstance(fs, (int, float, np.integer, np.floating)) and math.isfinite(fs) and 100 <= fs <= 1e7):
-            raise ValueError(f"fs must lie in 100 .. 1e7, got {fs!r}")
+        _batchio.check_fs(fs)
         f = np.asarray(freqs)
         if f.ndim != 1 or f.dtype.kind not in "fiu" or not 1 <= f.size <= MAX_FREQS:
             raise ValueError(f"freqs must be 1 .. {MAX_FREQS} numbers, got {freqs!r}")
@@ -105,11 +94,10 @@ class MtfBatch:
         x, is_np, squeeze, _ = _batchio.check_samples("MtfBatch", x, None)
         R, T = x.shape
         _batchio.check_streams(R)
-        if not 1 <= T <= MAX_SAMPLES:
-            raise ValueError(f"expected 1 .. 2^24 samples per row, got {T}")
+        _batchio.check_row_samples(T)
         _batchio.check_scratch_bytes(scratch_bytes)
-        lo = None if start is None else _row_integers("start", start, R, 0, T - 1)
-        hi = None if stop is None else _row_integers("stop", stop, R, 1, T)
+        lo = None if start is None else _batchio.row_integers("start", start, R, 0, T - 1, device=True)
+        hi = None if stop is None else _batchio.row_integers("stop", stop, R, 1, T, device=True)
         on_host = all(v is None or isinstance(v, np.ndarray) for v in (lo, hi))
         if is_np and not on_host:
             raise TypeError("start and stop on the device need x on the device")
@@ -240,30 +228,12 @@ def speech_transmission(ir, fs=48000, truncate="auto", filters="fir", order=3, *
     over the seven Butterworth band-passes of `order` (sosfilter.band_sos, forward or backwards in time) gives [S, 7, T] in
     float64, whose [7 S, T] view goes through one MtfBatch.run.  Then sti_from_mtf(m, **corrections) (snr_db, level_db, noise_db,
     weights, scheme)."""
-    if filters not in decay.FILTERS:
-        raise ValueError(f"filters={filters!r} ({', '.join(repr(f) for f in decay.FILTERS)})")
+    decay.check_filters(filters)
     centres, edges = decay.band_edges(octave_bands())
     broadband = decay.DecayBatch(fs=fs).run(ir, truncate=truncate)
     mtf = MtfBatch(MOD_FREQS, fs)
-    T = ir.shape[-1]
-    if filters != "fir":
-        from . import sosfilter
-        sos = np.stack([sosfilter.butter_band_sos(f_lo, f_hi, fs, order) for f_lo, f_hi in edges])
-        y = sosfilter.SosBatch(sos).run(ir, fan=True, reverse=filters == "butterworth-reversed", dtype="float64").y
-        m = mtf.run(y.reshape(-1, T), start=decay._per_band(broadband.onset, BANDS), stop=decay._per_band(broadband.truncation, BANDS)).m
-        m = m.reshape(tuple(ir.shape[:-1]) + (BANDS, len(MOD_FREQS)))
-        res = sti_from_mtf(m, **corrections)
-        return SpeechResult(centres, res.sti, res.mti, res.ti, m)
-    per_band = []
-    for f_lo, f_hi in edges:
-        h = decay.band_filter(f_lo, f_hi, fs)
-        M = (len(h) - 1) // 2
-        y = convolve.ConvolveBatch(h).run(ir).y
-        per_band.append(mtf.run(y[..., M:M + T], start=broadband.onset, stop=broadband.truncation).m)
-    if isinstance(ir, np.ndarray):
-        m = np.stack(per_band, -2)
-    else:
-        import torch
-        m = torch.stack(per_band, -2)
+    m = [mtf.run(rows, start=spread(broadband.onset), stop=spread(broadband.truncation)).m
+         for rows, spread in decay.band_front(ir, edges, fs, filters, order)]
+    m = decay.band_axis(ir, BANDS, filters, m)
     res = sti_from_mtf(m, **corrections)
     return SpeechResult(centres, res.sti, res.mti, res.ti, m)

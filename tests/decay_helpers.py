@@ -189,15 +189,24 @@ EDGE_BLOCKS = (8, 9, 63, 64, 65, 100, 512, 513, 1000, 2577, 65536)
 EDGE_FS = (8000, 11025, 44100, 96000, 192000)
 EDGE_SETTINGS = tuple([("onset_db", v) for v in (0.0, -6.0, -40.0, -60.0)] + [("noise_tail", v) for v in (0.001, 0.5, 1.0)] +
                       [("margin_db", v) for v in (0.0, 3.0, 25.0)])
-STRIDED_T = 66 * TILE + 5
-STRIDED_LEADS = (0, TILE - 1, TILE, 3)
+def strided_shape(tile):
+    """(T, the lead-ins) of the probes whose tile loops take a second trip in a launch of STRIDED_ROWS rows; sti_helpers.py's too."""
+    return 66 * tile + 5, (0, tile - 1, tile, 3)
+
+
+STRIDED_T, STRIDED_LEADS = strided_shape(TILE)
 STRIDED_ROWS = 520
 
 
+def tile_groups(rows, tiles):
+    """csrc/rowfront.h's tile_groups restated: the workgroups of 4 wavefronts per row in a launch of `rows` rows of `tiles` tiles."""
+    return min(-(-tiles // 4), max(16, -(-8192 // rows)))
+
+
 def strided(live_tiles, rows):
-    """Whether a wavefront of dk_totals / dk_scan (mtf_tiles) takes a second tile: a launch of `rows` rows holds
-    min(ceil(ntile / 4), max(16, ceil(8192 / rows))) workgroups of 4 wavefronts per row, and 4 ceil(ntile / 4) covers every tile."""
-    return live_tiles > 4 * max(16, -(-8192 // rows))
+    """Whether a wavefront of dk_totals / dk_scan (mtf_tiles) takes a second tile in a launch of `rows` rows (4 ceil(ntile / 4)
+    wavefronts cover every tile, so the row's own tile count does not matter)."""
+    return live_tiles > 4 * tile_groups(rows, live_tiles)
 
 
 def _frozen(x):

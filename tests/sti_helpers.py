@@ -10,7 +10,10 @@ import math
 
 import numpy as np
 
-from decay_helpers import response  # noqa: F401  (the seeded decaying-noise row)
+# the seeded decaying-noise row, what the strided cases share, and the two distances: max |got - want| and that over |want| (a
+# NaN or the same infinity on both sides is at distance 0, a NaN on one side at inf)
+from decay_helpers import STRIDED_ROWS, _frozen, response, strided_shape  # noqa: F401
+from decay_helpers import db_distance as distance, rel_distance as relative  # noqa: F401
 
 MOD_FREQS = (0.63, 0.8, 1.0, 1.25, 1.6, 2.0, 2.5, 3.15, 4.0, 5.0, 6.3, 8.0, 10.0, 12.5)
 ALPHA = {"male": (0.085, 0.127, 0.230, 0.233, 0.309, 0.224, 0.173), "female": (0.0, 0.117, 0.223, 0.216, 0.328, 0.250, 0.194)}
@@ -135,25 +138,6 @@ def two_sample_m(F, a, g, fs):
     return np.hypot(1 + g2 * np.cos(w), g2 * np.sin(w)) / (1 + g2)
 
 
-def distance(got, want):
-    """max |got - want|; a NaN or the same infinity on both sides is at distance 0, a NaN on one side at inf."""
-    got, want = np.asarray(got, np.longdouble), np.asarray(want, np.longdouble)
-    same = (got == want) | (np.isnan(got) & np.isnan(want))
-    with np.errstate(invalid="ignore"):
-        d = np.abs(got - want)
-    d = np.where(same, 0, np.where(np.isnan(d), np.inf, d))
-    return float(np.max(d)) if d.size else 0.0
-
-
-def relative(got, want):
-    got, want = np.asarray(got, np.longdouble), np.asarray(want, np.longdouble)
-    same = (got == want) | (np.isnan(got) & np.isnan(want))
-    with np.errstate(invalid="ignore", divide="ignore"):
-        d = np.abs(got - want) / np.abs(want)
-    d = np.where(same, 0, np.where(np.isnan(d), np.inf, d))
-    return float(np.max(d)) if d.size else 0.0
-
-
 def compare(res, ref, label, m_bar=1e-10, energy_bar=1e-10):
     """Prints the distances of an MtfResult (numpy fields) from the reference (m, energy), then asserts the bars: absolute on m,
     relative on energy."""
@@ -170,14 +154,7 @@ LEADS = (0, TILE - 1, TILE)
 EDGE_T = 2 * TILE + 3
 OFF_DEFAULT = ((44100, (0.63, 3.15, 12.5, 997.0, 22049.5)), (100, (0.63, 7.3, 49.9)), (96000, (0.001, 1.0, 47999.0)),
                (22050.5, (0.63, 3.0, 10000.25)), (48000, MOD_FREQS[-9:]))
-STRIDED_T = 66 * TILE + 5
-STRIDED_LEADS = (0, TILE - 1, TILE, 3)
-STRIDED_ROWS = 520
-
-
-def _frozen(x):
-    x.setflags(write=False)
-    return x
+STRIDED_T, STRIDED_LEADS = strided_shape(TILE)
 
 
 def seam_rows(T, rows, f32):

@@ -129,6 +129,39 @@ def test_arguments_are_checked_before_the_library():
         db.run(x, scratch_bytes=-1)
 
 
+def test_row_integers_of_the_row_chains():
+    """_batchio.row_integers, which DecayBatch (onset, truncate) and MtfBatch (start, stop) share, at R = 3."""
+    from friture_amd import _batchio
+    v = _batchio.row_integers("onset", [0, 5, 999], 3, 0, 999)
+    assert v.dtype == np.int64 and v.shape == (3,) and v.flags.c_contiguous and v.tolist() == [0, 5, 999]
+    assert _batchio.row_integers("stop", np.int32(7), 3, 1, 1000, device=True).tolist() == [7, 7, 7]       # shape (): every row
+    for bad in ([0.0, 1.0, 2.0], np.float32(1), [0, 1], [[0, 1, 2]]):
+        with pytest.raises(ValueError, match=r"onset must be integers \[3\], got "):
+            _batchio.row_integers("onset", bad, 3, 0, 999)
+    with pytest.raises(ValueError, match=r"onset must lie in 0 \.\. 999, got -1 \.\. 2"):
+        _batchio.row_integers("onset", [0, -1, 2], 3, 0, 999)
+    with pytest.raises(ValueError, match=r"truncate must lie in 1 \.\. 1000, got 1 \.\. 1001"):
+        _batchio.row_integers("truncate", [1, 2, 1001], 3, 1, 1000)
+
+
+@pytest.mark.parametrize("filters", decay.FILTERS)
+def test_band_axis_is_the_way_back_from_the_band_front(filters):
+    """Numpy stand-ins for what a consumer made of band_front's pairs, S = 2, B = 3: one result [S, ..] per band of "fir", one
+    [S B, ..] of the bank, response-major.  Entry (s, b) comes back at [s, b]."""
+    S, B = 2, 3
+    flat, r2 = np.arange(S * B, dtype=np.float64), np.arange(S * B * 4, dtype=np.float64).reshape(S * B, 4)
+    if filters == "fir":
+        made = lambda v, lead: [v.reshape(lead + (B,) + v.shape[1:]).take(b, len(lead)) for b in range(B)]
+    else:
+        made = lambda v, lead: [v]
+    ir = np.zeros((S, 100))
+    got, got_r2 = decay.band_axis(ir, B, filters, made(flat, (S,))), decay.band_axis(ir, B, filters, made(r2, (S,)))
+    assert got.shape == (2, 3) and np.array_equal(got, flat.reshape(2, 3))
+    assert got_r2.shape == (2, 3, 4) and np.array_equal(got_r2, r2.reshape(2, 3, 4))
+    one = decay.band_axis(ir[0], B, filters, made(flat[:B], ()))
+    assert one.shape == (3,) and np.array_equal(one, flat[:B])
+
+
 def test_binding_table_lists_the_entry_points():
     names = {n for n in _lib.SIGNATURES if n.startswith("frt_decay_")}
     assert names == {"frt_decay_tile", "frt_decay_create", "frt_decay_destroy", "frt_decay_set_stream", "frt_decay_run"}

@@ -83,7 +83,8 @@ def test_strided_batch_takes_a_second_trip(mod):
     per_row = (2 * -(-dh.STRIDED_T // 16) + 23 * -(-dh.STRIDED_T // TL)) * 8 + 112          # decay.hip: doubles and the row record
     assert (1 << 28) // per_row >= dh.STRIDED_ROWS                                           # one slab
     spans = dh.live_tiles([r["onset"] for r in refs], [r["truncation"] for r in refs])
-    assert all(n > 4 * max(16, -(-8192 // dh.STRIDED_ROWS)) for n in spans) and spans.tolist() == [67, 66, 66, 67]
+    groups = dh.tile_groups(dh.STRIDED_ROWS, -(-dh.STRIDED_T // TL))
+    assert groups == 16 and all(n > 4 * groups for n in spans) and spans.tolist() == [67, 66, 66, 67]
     _strided_batch(mod, "one launch of 520 rows, two trips")
 
 
@@ -93,7 +94,8 @@ def test_strided_batch_in_slabs_of_one_trip(mod):
     per_row = (2 * -(-dh.STRIDED_T // 16) + 23 * -(-dh.STRIDED_T // TL)) * 8 + 112
     scratch = 101 * per_row + 8
     slab = scratch // per_row
-    assert slab == 101 and not 67 > 4 * max(16, -(-8192 // slab)) and not 67 > 4 * max(16, -(-8192 // (dh.STRIDED_ROWS % slab)))
+    groups = [dh.tile_groups(rows, 67) for rows in (slab, dh.STRIDED_ROWS % slab)]
+    assert slab == 101 and groups == [17, 17] and not 67 > 4 * min(groups)
     _strided_batch(mod, "slabs of 101 rows, one trip", scratch_bytes=scratch)
 
 

@@ -251,6 +251,73 @@ def test_room_acoustics_against_the_numpy_pipeline(mod):
             print(f"  response {s}, {centres[b]:.0f} Hz: T30 {res.t30[s]:.5f} s, design rt {rts[s][b]:.5f} s")
 
 
+@functools.lru_cache(maxsize=None)
+def front_case():
+    ir = np.stack([dh.response(6000, 0.03, 300 + s, lead=100 + 30 * s) for s in range(2)])
+    ir.setflags(write=False)
+    return ir
+
+
+def bits_of(a):
+    a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+    return a.dtype, a.shape, a.tobytes()
+
+
+@pytest.mark.parametrize("filters", ["fir", "butterworth"])
+def test_room_acoustics_is_its_composition_bit_for_bit(mod, filters):
+    """S = 2 responses of T = 6000 samples, two bands: room_acoustics against the calls it stands for, written out.  "fir":
+    per band, band_filter, ConvolveBatch(h).run(ir).y[..., M : M + T], DecayBatch.run with the broadband onsets.  "butterworth":
+    SosBatch(..).run(fan=True) and one DecayBatch.run on its [S B, T] view with the onsets repeated per band."""
+    from friture_amd import convolve, sosfilter
+    ir, bands, T = front_case(), [(500, 1000), (1000, 2000)], 6000
+    room = mod.room_acoustics(ir, bands=bands, filters=filters)
+    db = mod.DecayBatch()
+    broadband = db.run(ir)
+    same_bits(room.broadband, broadband)
+    if filters == "fir":
+        per_band = []
+        for f_lo, f_hi in bands:
+            h = mod.band_filter(f_lo, f_hi, FS)
+            M = (len(h) - 1) // 2
+            per_band.append(db.run(convolve.ConvolveBatch(h).run(ir).y[..., M:M + T], onset=broadband.onset))
+        want = {f: np.stack([getattr(r, f) for r in per_band], 1) for f in dh.FLOATS + dh.INDICES + ("r2",)}
+    else:
+        sos = np.stack([sosfilter.butter_band_sos(f_lo, f_hi, FS, 3) for f_lo, f_hi in bands])
+        y = sosfilter.SosBatch(sos).run(ir, fan=True, dtype="float64").y
+        assert y.shape == (2, 2, T)
+        res = db.run(y.reshape(4, T), onset=np.repeat(broadband.onset, 2))
+        want = {f: getattr(res, f).reshape((2, 2) + getattr(res, f).shape[1:]) for f in dh.FLOATS + dh.INDICES + ("r2",)}
+    assert room.bands.curve is None and room.bands.edt.shape == (2, 2) and room.bands.r2.shape == (2, 2, 4)
+    assert not np.any(np.isnan(room.bands.t20))
+    for f, v in want.items():
+        assert bits_of(getattr(room.bands, f)) == bits_of(v), f
+
+
+@pytest.mark.parametrize("filters", ["fir", "butterworth"])
+def test_speech_transmission_is_its_composition_bit_for_bit(mod, filters):
+    """The same responses through speech_transmission's seven octaves: MtfBatch.run over [onset, truncation) of the broadband
+    DecayBatch.run, on the delayed views per band or on the bank's [S B, T] view, then sti_from_mtf."""
+    from friture_amd import convolve, sosfilter, sti
+    ir, T = front_case(), 6000
+    got = sti.speech_transmission(ir, filters=filters)
+    broadband = mod.DecayBatch().run(ir)
+    mtf = sti.MtfBatch()
+    if filters == "fir":
+        per_band = []
+        for f_lo, f_hi in sti.octave_bands():
+            h = mod.band_filter(f_lo, f_hi, FS)
+            M = (len(h) - 1) // 2
+            per_band.append(mtf.run(convolve.ConvolveBatch(h).run(ir).y[..., M:M + T], start=broadband.onset, stop=broadband.truncation).m)
+        m = np.stack(per_band, 1)
+    else:
+        sos = np.stack([sosfilter.butter_band_sos(f_lo, f_hi, FS, 3) for f_lo, f_hi in sti.octave_bands()])
+        y = sosfilter.SosBatch(sos).run(ir, fan=True, dtype="float64").y
+        m = mtf.run(y.reshape(14, T), start=np.repeat(broadband.onset, 7), stop=np.repeat(broadband.truncation, 7)).m.reshape(2, 7, 14)
+    assert got.m.shape == (2, 7, 14) and not np.any(np.isnan(got.m)) and bits_of(got.m) == bits_of(m)
+    for a, b in zip(got[1:4], sti.sti_from_mtf(m)):
+        assert bits_of(a) == bits_of(b)
+
+
 def test_a_bad_argument_through_the_c_entry_point(mod):
     from friture_amd import _lib
     h = _lib.Handle("decay", 48000.0, 480, -20.0, 0.1, 10.0)

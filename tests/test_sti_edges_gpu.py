@@ -77,7 +77,8 @@ def test_strided_batch_takes_a_second_trip(mod):
     per_row = -(-sh.STRIDED_T // TL) * (1 + 2 * 14) * 8              # mtf.hip: 1 + 2 nf doubles per tile
     assert (1 << 28) // per_row >= sh.STRIDED_ROWS                   # one slab
     spans = dh.live_tiles(start, [sh.STRIDED_T] * 4, TL)
-    assert all(n > 4 * max(16, -(-8192 // sh.STRIDED_ROWS)) for n in spans) and spans.tolist() == [67, 67, 66, 67]
+    groups = dh.tile_groups(sh.STRIDED_ROWS, -(-sh.STRIDED_T // TL))
+    assert groups == 16 and all(n > 4 * groups for n in spans) and spans.tolist() == [67, 67, 66, 67]
     _strided_batch(mod, "one launch of 520 rows, two trips")
 
 
@@ -87,7 +88,8 @@ def test_strided_batch_in_slabs_of_one_trip(mod):
     per_row = -(-sh.STRIDED_T // TL) * (1 + 2 * 14) * 8
     scratch = 101 * per_row + 8
     slab = scratch // per_row
-    assert slab == 101 and not 67 > 4 * max(16, -(-8192 // slab)) and not 67 > 4 * max(16, -(-8192 // (sh.STRIDED_ROWS % slab)))
+    groups = [dh.tile_groups(rows, 67) for rows in (slab, sh.STRIDED_ROWS % slab)]
+    assert slab == 101 and groups == [17, 17] and not 67 > 4 * min(groups)
     _strided_batch(mod, "slabs of 101 rows, one trip", scratch_bytes=scratch)
 
 
