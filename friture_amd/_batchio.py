@@ -1,10 +1,10 @@
 """What the batch classes share.  All of them (LevelsBatch, ScopeBatch, CurveBatch, SpectrumBatch, SpectrogramBatch, PitchBatch,
-OctaveSpectrumBatch, DelayEstimatorBatch, Resampler, LoudnessBatch, TransferBatch, ConvolveBatch, DecayBatch, DeconvolveBatch, MtfBatch, SosBatch): their input is a float32/float64
+OctaveSpectrumBatch, DelayEstimatorBatch, Resampler, LoudnessBatch, TransferBatch, ConvolveBatch, DecayBatch, DeconvolveBatch, MtfBatch, SosBatch, SoundLevelBatch): their input is a float32/float64
 numpy array or CUDA tensor and their results are of the same kind (ptr, source, alloc).  The widget batches: a recording is seen
 in chunks (chunk_ends, checked_ends, frame_schedule); for the five chains over recordings, the host side of run(): the input
 checks (check_keep, check_samples; `dual` for two rows per stream), the hand-over to the null stream, the device copy of a
 carried state (carried) and the way back to numpy (to_host); for the two STFT chains, the sample front (RecordingFront).  The
-recording chains (Resampler, LoudnessBatch, TransferBatch, ConvolveBatch, DecayBatch, DeconvolveBatch, MtfBatch, SosBatch): the checks of the stream count and of scratch_bytes,
+recording chains (Resampler, LoudnessBatch, TransferBatch, ConvolveBatch, DecayBatch, DeconvolveBatch, MtfBatch, SosBatch, SoundLevelBatch): the checks of the stream count and of scratch_bytes,
 the rows read in place (strided_rows) and the numpy / CUDA fork of run() (run_call).  The chains over rows of samples (DecayBatch,
 MtfBatch; rowfront.h is their library side): the checks of fs and of the samples per row (check_fs, check_row_samples) and the
 per-row integers of onset / truncate / start / stop (row_integers)."""

@@ -217,6 +217,15 @@ SIGNATURES = {
     "frt_sos_set_stream": (c_int, [c_void_p, c_void_p]),
     "frt_sos_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_int64,
                             c_void_p, c_int]),
+    "frt_spl_default_cell": (c_int, [c_int]),
+    "frt_spl_state_length": (c_int, [c_int]),
+    "frt_spl_intervals_for": (c_int64, [c_int, c_int64, c_int64, c_int]),
+    "frt_spl_tables": (c_int, [c_double, POINTER(c_double), c_int, c_int, c_int] + [POINTER(c_double)] * 4),
+    "frt_spl_create": (c_int, [POINTER(c_void_p), c_double, POINTER(c_double), c_int, c_int, c_int]),
+    "frt_spl_destroy": (None, [c_void_p]),
+    "frt_spl_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_spl_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int64, c_void_p,
+                            c_void_p, POINTER(c_int64)]),
     "frt_lfilter_f64":(c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

@@ -43,6 +43,7 @@ EXTRA_FLAGS = {"iir.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-for
                "deconvolve.hip": ["-ffp-contract=off"],      # X4: every product of the transform and of Y G rounds on its own
                "mtf.hip": ["-ffp-contract=off"],             # X5: the fused multiply-adds of the sums are the ones written out
                "sosfilter.hip": ["-ffp-contract=off"],       # X6: every product of a section and of a scan step rounds on its own
+               "soundlevel.hip": ["-ffp-contract=off"],      # X7: a e + g q and P + A s round each product on its own
                "stft.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"]}
 
 

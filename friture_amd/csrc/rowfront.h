@@ -1,4 +1,4 @@
-// rowfront.h — what the entries over rows of samples share (frt_decay_run, frt_mtf_run, frt_sos_run): the wavefront folds of
+// rowfront.h — what the entries over rows of samples share (frt_decay_run, frt_mtf_run, frt_sos_run, frt_spl_run): the wavefront folds of
 // their kernels, the opening of the entry, the row slabs that keep a launch's scratch within scratch_bytes, the workgroups per
 // row of a tile loop, and the end of a handle.  (convolve.hip, deconvolve.hip, transfer.hip and loudness.hip cut their scratch
 // into windows and runs, not rows.)

@@ -16,7 +16,7 @@ absolute sample index, the cell transition M = A^cell and M^64 made on the host 
 A stream of at most `cell` samples is the sequential filter bit for bit; a longer one differs from it by rounding alone.  A
 recording cut into calls at any sample, any scratch_bytes, batch, row stride, input dtype and host or device buffers give the
 bits of one whole call: run() returns the state that continues the streams.  Out of scope: design families other than
-Butterworth band-passes, padding or steady-state initial conditions for zero-phase use, decimating banks, a live chunk object.
+Butterworth band-passes (the A and C weightings are in soundlevel.py), padding or steady-state initial conditions for zero-phase use, decimating banks, a live chunk object.
 There is no CPU fallback: run() goes to the HIP library."""
 from __future__ import annotations
 

@@ -1139,6 +1139,74 @@ int frt_sos_set_stream(frt_sos* h, void* hip_stream);
 int frt_sos_run(frt_sos* h, const void* x, int x_dtype, int rows, int64_t n, int64_t row_stride, int fan, int reverse,
                 int64_t n_before, const double* state_in, double* state_out, int64_t scratch_bytes, void* y, int y_dtype);
 
+/* ---- X7: the detector of a sound level meter (IEC 61672-1 time weightings, interval logging) (SoundLevelBatch) --------------------
+ * The reference has no such component; this is the definition.
+ * Input: rows w [R][T] of float32 or float64 samples that are ALREADY frequency weighted (the A and C weightings and band filters
+ * are X6 cascades: friture_amd/soundlevel.py); float32 widens exactly.  Settings, fixed at creation: fs; 1 .. 4 time constants
+ * tau_i (Fast 0.125 s, Slow 1 s); the logging interval I, a multiple of 16 in 16 .. 2^20 samples; the cell size, a multiple of
+ * 16 in 16 .. 1024 that divides I.  All arithmetic is float64, every product rounded on its own (no fused multiply-add).
+ * Per sample n of the stream (n counts from the stream's first sample, over all calls):
+ *    q[n] = w[n] w[n];   e_i[n] = a_i e_i[n-1] + g_i q[n],  e_i[-1] = 0
+ * a_i = exp(-1 / (fs tau_i)) and g_i = -expm1(-1 / (fs tau_i)), both made on the host in long double (-1 / (fs tau_i) too) and
+ * rounded once.
+ * Time-parallel order.  A row is cut into cells of `cell` samples on a grid anchored at the stream's absolute sample index; 64
+ * consecutive cells on that grid are a run.  A_i = a_i^cell, made on the host in long double as the product 1 a a .. a (cell
+ * factors of the rounded a_i, left to right) and rounded once; A64_i = the same product of 64 cell factors.  Per time constant:
+ *    P_c = e behind cell c stepped sample by sample from e = 0;
+ *    Q_r = the cells of run r chained from zero: q <- P_c + A q, c ascending;
+ *    U_0 = 0, U_(r+1) = Q_r + A64 U_r: the true value in front of run r + 1;
+ *    S_c = U_r for a run's first cell, otherwise S_(c+1) = P_c + A S_c: the true value in front of cell c;
+ *    e over cell c = the recurrence stepped sample by sample from S_c (second pass).
+ * A stream of at most `cell` samples is therefore the sequential recurrence, bit for bit.
+ * Per interval j, the samples [j I, (j + 1) I) of the stream:
+ *    energy[j] = the sums of its cells added in ascending order from 0, a cell's sum being its q added in ascending order from 0;
+ *    peak[j]   = max |w|;
+ *    last_i[j] = e_i at the interval's last sample;  max_i[j], min_i[j] = the extrema of e_i over the interval's samples.
+ * Without flush a call emits the intervals that its last sample completes; flush = 1 also emits the partial last interval (its
+ * partial last cell's sum is added last) with count[j] < I, and the state is then final.  Stream totals cover the emitted
+ * intervals: the energies added in ascending order, the peak, the extrema per time constant.
+ * A NaN sample makes e_i NaN from that sample on: last, max and min are NaN from its interval on (maxima and minima keep a NaN
+ * explicitly), energy and peak are NaN in its own interval only; earlier intervals and other rows keep their bits.  An infinite
+ * sample makes the averages not finite from there on.  An all-zero row gives exact zeros.
+ * The bits of a row's results depend on its own samples, the settings and the absolute sample index: on no other row, slab
+ * size, row stride, input dtype, or host against device buffers, and not on how the stream was cut into calls.  The state behind
+ * n samples is, per row, nine vectors of ntau doubles and five scalars (frt_spl_state_length = 9 ntau + 5): the running e at n
+ * (S_c itself when n lies on the cell grid), the partial zero-state run of the cell that holds n, S_c of that cell, the partial q
+ * of its run, U_r of its run, the open interval's maximum and minimum, the totals' maximum and minimum; then the open cell's
+ * sum of q, the open interval's energy (its complete cells) and peak, the totals' energy and peak.  n itself travels beside it
+ * (n_before); the totals' sample count is n_before rounded down to the interval grid, or all of it after a flush.
+ * Out of scope: the Impulse time weighting; class conformity claims for a whole instrument; sample rates at which the bilinear
+ * transform of the A and C weightings deviates more (the deviation is documented, not corrected: soundlevel.py); fusing the
+ * weighting cascade into the detector pass; a live chunk object; percentiles carried in the state. */
+typedef struct frt_spl frt_spl;
+/* pure host: the cell size that cell = 0 stands for, the largest admissible one up to 400 (0: a bad interval); the doubles of a
+ * state per row (0: ntau outside 1 .. 4); the intervals a call of n samples behind n_before emits (-1: a bad argument) */
+int frt_spl_default_cell(int interval);
+int frt_spl_state_length(int ntau);
+int64_t frt_spl_intervals_for(int interval, int64_t n_before, int64_t n, int flush);
+/* pure host: a, g, A and A64 [ntau] as a handle of these settings holds them; each may be NULL.  The checks are those of
+ * frt_spl_create. */
+int frt_spl_tables(double fs, const double* taus, int ntau, int interval, int cell, double* a, double* g, double* A, double* A64);
+/* taus: [ntau] HOST doubles, seconds.  cell: 0 for the default.  FRT_ERR_INVALID, before any device call: a null pointer, fs
+ * outside 100 .. 1e7, ntau outside 1 .. 4, a time constant that is not finite and positive or whose a rounds to 0 or 1, an
+ * interval that is no multiple of 16 in 16 .. 2^20, a cell that is no multiple of 16 in 16 .. 1024 or does not divide it. */
+int frt_spl_create(frt_spl** h, double fs, const double* taus, int ntau, int interval, int cell);
+void frt_spl_destroy(frt_spl* h);
+/* Launches go to the null stream unless another one is set here. */
+int frt_spl_set_stream(frt_spl* h, void* hip_stream);
+/* One call over `rows` rows of n samples, 1 <= n <= 2^24: sample t of row r is x[r row_stride + t] (stride in elements, >= n),
+ * float32 (x_dtype 0) or float64 (1).  n_before: the samples the streams have seen; state_in [rows][frt_spl_state_length] or
+ * NULL (fresh streams, n_before 0); state_out likewise or NULL, not overlapping state_in.  J = frt_spl_intervals_for(I, n_before,
+ * n, flush) intervals are emitted (also returned in *n_intervals, a HOST pointer or NULL): vals [rows][J][2 + 3 ntau] = energy,
+ * peak, last_0 .., max_0 .., min_0 ..; count [J] = the samples of each.  The rows are cut into slabs whose scratch stays within
+ * scratch_bytes (at least one row per launch); the result does not depend on it.  Host or device buffers in any mix (host
+ * ones are staged); one synchronisation at the end.  FRT_ERR_INVALID, before any launch: a null handle or x, vals or count
+ * null with J > 0, an unknown dtype, rows outside 1 .. 65535, n outside 1 .. 2^24, a bad stride, flush other than 0 or 1,
+ * n_before without state_in or negative, scratch_bytes < 0. */
+int frt_spl_run(frt_spl* h, const void* x, int x_dtype, int rows, int64_t n, int64_t row_stride, int64_t n_before,
+                const double* state_in, double* state_out, int flush, int64_t scratch_bytes, double* vals, int64_t* count,
+                int64_t* n_intervals);
+
 #ifdef __cplusplus
 }
 #endif
