@@ -1,6 +1,8 @@
 """References for SosBatch (X6), numpy only: (i) the sequential recurrence in np.longdouble, (ii) the same in float64, (iii) a
 float64 restatement of the cell form (M rounded from long double, then passes 1, 2 and 3), the accuracy bar made from (i) and (ii),
-and the closed-form impulse response of a cascade.  Everything is vectorised over the output rows (input row, filter)."""
+the closed-form impulse response of a cascade, the inputs that the CPU and the GPU tests share (the seams, the banks, and the
+edge inputs of test_sos_edges_*.py behind the sections(K) / bank(F, K) builders), and the comparisons that the GPU test files
+share.  Everything is vectorised over the output rows (input row, filter)."""
 import functools
 
 import numpy as np
@@ -53,16 +55,13 @@ def sequential(x, sos, fan=False, dtype=np.float64, reverse=False):
 
 
 def transition(coef, steps):
-    """M [N, 2K, 2K] float64: state i after `steps` samples of silence from the unit state j, stepped in long double."""
+    """M [N, 2K, 2K] float64: state i after `steps` samples of silence from the unit state j, stepped in long double (all the
+    unit states of all rows in one walk)."""
     N, K = coef.shape[:2]
-    M = np.empty((N, 2 * K, 2 * K))
-    silence = np.zeros((N, steps))
-    for j in range(2 * K):
-        z = np.zeros((N, 2 * K), np.longdouble)
-        z[:, j] = 1
-        _steps(silence, coef, z, np.longdouble)
-        M[:, :, j] = z.astype(np.float64)
-    return M
+    S2 = 2 * K
+    z = np.tile(np.eye(S2, dtype=np.longdouble), (N, 1))         # row n * 2K + j: filter n from the unit state j
+    _steps(np.zeros((N * S2, steps)), np.repeat(coef, S2, axis=0), z, np.longdouble)
+    return np.ascontiguousarray(z.reshape(N, S2, S2).transpose(0, 2, 1).astype(np.float64))
 
 
 def _matvec(M, s, p):
@@ -185,3 +184,127 @@ def _bank(bands):
 
 
 INPUTS.update(seam=_seam, bank=_bank)
+
+
+# ---- the edge inputs: every section count, cell size, walk length and bank width (test_sos_edges_cpu.py / _gpu.py) ----------------
+
+EDGE_CELL = 32
+SECTION_COUNTS = tuple(range(1, 9))
+SECTIONS_LENGTH = 64 * 32 + 33                                   # two runs at cell 32: one step of level two, from U_0 = 0
+THREE_RUNS_LENGTH = 2 * 64 * 32 + 33                             # three runs: the second step multiplies M^64 by a U that is not 0
+WALK_CENTRE = 16.0                                               # an octave whose state outlives a run of 2048 samples: M^64 has entries of 85
+CELLS = (64, 128, 256, 512, 1024)
+WALK_RUNS = (17, 18, 33, 34)                                     # 16, 17, 32 and 33 steps of level two: whole rounds of 16 and one more
+WIDTHS = (1, 4, 64)
+STIFF_KINDS = ("band20", "A", "C")
+STIFF_CELLS = (32, 256)
+CENTRES = {1: (1000.0,), 3: (125.0, 1000.0, 8000.0), 4: (125.0, 500.0, 2000.0, 8000.0), 5: (125.0, 500.0, 1000.0, 4000.0, 8000.0),
+           64: tuple(np.geomspace(100.0, 10000.0, 64).tolist())}
+
+
+def sections(K, centre=1000.0):
+    """The Butterworth band-pass of order K (K sections) one octave wide around `centre` at 48 kHz: [K, 6]."""
+    from friture_amd import sosfilter
+    return sosfilter.butter_band_sos(centre / 2 ** 0.5, centre * 2 ** 0.5, 48000, K)
+
+
+def bank(F, K):
+    """F such filters on the centres CENTRES[F]: [F, K, 6]."""
+    return np.stack([sections(K, f) for f in CENTRES[F]])
+
+
+def run_edge_length(cell):
+    """65 cells and 17 samples: one run seam, one step of level two, a partial last cell."""
+    return 65 * cell + 17
+
+
+def walk_length(nr):
+    """nr runs at cell 32, the last one of five samples: nr - 1 steps of level two."""
+    return (nr - 1) * 64 * EDGE_CELL + 5
+
+
+def _sections(K, mode):
+    seed = 100 + 2 * K + (mode == "bank")
+    if mode == "bank":                                           # 2 rows into five bands: the second filter group has three idle waves
+        return decaying_noise(2, SECTIONS_LENGTH, seed), bank(5, K), True
+    return decaying_noise(3, SECTIONS_LENGTH, seed), bank(5, K)[[0, 3]], False       # row r through filter r % 2
+
+
+def _three_runs(K):
+    return decaying_noise(1, THREE_RUNS_LENGTH, 150 + K), bank(5, K), True
+
+
+def _cells(cell):
+    return decaying_noise(1, run_edge_length(cell), 200 + cell), bank(3, 3), True
+
+
+def _walk(nr):
+    return decaying_noise(1, walk_length(nr), 300 + nr), sections(1, WALK_CENTRE)[None], False
+
+
+def _width(F):
+    return decaying_noise(1, 2 * EDGE_CELL + 1, 400 + F), bank(F, 1), True
+
+
+def stiff_sos(kind):
+    """The 20 Hz third-octave of order 4, the A weighting (K = 3) and the C weighting (K = 2), both weightings with a double real
+    pole at 20.6 Hz: [K, 6]."""
+    from friture_amd import sosfilter, soundlevel
+    return sosfilter.butter_band_sos(17.8, 22.4, 48000, 4) if kind == "band20" else soundlevel.weighting_sos(kind)
+
+
+def _stiff(kind, cell):
+    x = decaying_noise(2, run_edge_length(cell), 500 + cell + STIFF_KINDS.index(kind), rt=2.0)
+    return x, stiff_sos(kind)[None], False
+
+
+INPUTS.update(sections=_sections, three_runs=_three_runs, cells=_cells, walk=_walk, width=_width, stiff=_stiff)
+
+# (name, args, cell) of every edge input that has a long double reference
+EDGE_INPUTS = ([("sections", (K, mode), EDGE_CELL) for K in SECTION_COUNTS for mode in ("bank", "row")]
+               + [("three_runs", (K,), EDGE_CELL) for K in SECTION_COUNTS]
+               + [("cells", (cell,), cell) for cell in CELLS] + [("walk", (nr,), EDGE_CELL) for nr in WALK_RUNS]
+               + [("width", (F,), EDGE_CELL) for F in WIDTHS] + [("stiff", (kind, cell), cell) for kind in STIFF_KINDS for cell in STIFF_CELLS])
+
+
+# ---- what the GPU test files share -------------------------------------------------------------------------------------------------
+
+def host(v):
+    return v.cpu().numpy() if hasattr(v, "cpu") else v
+
+
+def same_bits(a, b):
+    a, b = host(a), host(b)
+    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def same_state(a, b):
+    assert a.rows == b.rows and a.n == b.n and a.settings == b.settings
+    same_bits(a.data, b.data)
+
+
+def led(x, lead):
+    """x as a view that starts `lead` elements into a buffer."""
+    buf = np.zeros(lead + x.size, x.dtype)
+    buf[lead:] = x.reshape(-1)
+    return buf[lead:].reshape(x.shape)
+
+
+def run_pieces(batch, x, cuts, fan):
+    state, parts = None, []
+    for a, b in zip([0] + list(cuts), list(cuts) + [x.shape[-1]]):
+        r = batch.run(x[..., a:b], fan=fan, state=state)
+        state = r.state
+        parts.append(host(r.y))
+    return np.concatenate(parts, axis=-1), state
+
+
+def parity(y, name, args, label):
+    """Prints and asserts the distance of y from the long double reference of the named input; returns the worst distance / bar."""
+    x, sos, fan, yld, y64 = cached(name, *args)
+    y = host(y).astype(np.float64).reshape(yld.shape)
+    e, d, b = distance(y64, yld), distance(y, yld), bar(y64, yld)
+    print(f"{label}: e_seq {e.max():.2e}, device {d.max():.2e}, largest device / e_seq {(d / np.maximum(e, 1e-300)).max():.1f}, "
+          f"bar {b.min():.2e} .. {b.max():.2e}, worst device / bar {(d / b).max():.3f}")
+    assert np.all(d <= b)
+    return float((d / b).max())

@@ -1,13 +1,14 @@
 """References for SoundLevelBatch's detector (X7), numpy only: (i) the sequential recurrence e = a e + g q in np.longdouble, (ii)
 the same in float64, (iii) a float64 restatement of the cell form (the tables rounded from long double, pass 1, the two-level
 scan, pass 2, the folds over cells and intervals), the accuracy bar made from (i) and (ii) as tests/sos_helpers.py makes it, and
-the inputs that the CPU and the GPU tests share.  Everything is vectorised over the rows and the time constants."""
+the inputs and settings that the CPU and the GPU tests share (the seams, and the edge settings of test_soundlevel_edges_*.py), and the
+comparisons that the GPU test files share.  Everything is vectorised over the rows and the time constants."""
 import functools
 from collections import namedtuple
 
 import numpy as np
 
-from sos_helpers import decaying_noise
+from sos_helpers import decaying_noise, led  # noqa: F401 (led: for the GPU test files)
 
 RUN = 64
 FS = 48000.0
@@ -176,12 +177,132 @@ def long_input():
     return decaying_noise(2, LONG_LENGTH, 23, rt=1.0)
 
 
+UNIT_AT = 703
+
+
+def unit_and_noise(T):
+    """Three rows: a unit sample followed by silence, decaying noise, and silence around a unit sample at UNIT_AT (the last sample
+    of cell 0 at cell 704, so that cell 2 starts from A times a normal number)."""
+    w = decaying_noise(3, T, 3 * T + 1, rt=1.0)
+    w[[0, 2]] = 0.0
+    w[0, 0] = w[2, UNIT_AT] = 1.0
+    return w
+
+
+INPUTS = {"f64x3": lambda T: seam_input("f64x3", T), "f32x65": lambda T: seam_input("f32x65", T), "long": lambda T: long_input(),
+          "f64x1": lambda T: decaying_noise(1, T, 3 * T + 2, rt=1.0), "f64x2": lambda T: decaying_noise(2, T, 3 * T + 3, rt=1.0),
+          "unit+noise": unit_and_noise}
+
+
+def cached(kind, T, fs, taus, cell, interval):
+    """The references of one named input at the given settings, made once per process and keyed by (kind, T, fs, taus, cell,
+    interval): (w, Fields in long double, Fields in float64 sequential, bar [R, ntau], the averages' maxima [R, ntau])."""
+    return _cached(kind, int(T), float(fs), tuple(float(t) for t in taus), int(cell), int(interval))
+
+
 @functools.lru_cache(maxsize=None)
-def cached(kind, T):
-    """The references of one shared input at the SEAM settings, made once per process: (w, Fields in long double, Fields in
-    float64 sequential, bar [R, ntau], the averages' maxima [R, ntau])."""
-    w = long_input() if kind == "long" else seam_input(kind, T)
-    a, g, _, _ = tables(SEAM["fs"], SEAM["taus"], SEAM["cell"])
+def _cached(kind, T, fs, taus, cell, interval):
+    w = INPUTS[kind](T)
+    a, g, _, _ = tables(fs, taus, cell)
     eld, e64 = sequential(w, a, g, np.longdouble), sequential(w, a, g, np.float64)
     b, peak = bar(e64, eld)
-    return w, fields(w, eld, SEAM["interval"]), fields(w, e64, SEAM["interval"]), b, peak
+    return w, fields(w, eld, interval), fields(w, e64, interval), b, peak
+
+
+def worst_ratio(got, ref, seq_bar, e_peak):
+    """The largest distance / bar over last, max and min: the figure the parity tests print."""
+    return max(float((distance(getattr(got, n), getattr(ref, n), e_peak) / seq_bar).max()) for n in ("last", "max", "min"))
+
+
+# ---- the edge settings: every number of time constants, cell and interval extremes, walk lengths, table extremes ------------------
+# (test_soundlevel_edges_cpu.py / _gpu.py); a case is (kind, T, settings)
+
+def edge(kind, T, taus, cell, interval, fs=FS):
+    return kind, T, dict(interval=interval, cell=cell, taus=taus, fs=fs)
+
+
+EDGE_TAUS = {1: (0.002,), 3: (0.002, 0.02, 0.035), 4: (0.002, 0.02, 0.125, 1.0)}
+TAUS_LENGTHS = (2049, 64 * 32 + 33, 2 * 64 * 32 + 33)                # the last: three runs, so that A64 meets a U that is not 0
+PIECES_LENGTH = 64 * 32 + 33
+PIECE_CUTS = (1, 31, 32, 33, 480, 1000, 2049)                      # of the longer row
+LONG_INTERVAL_LENGTH = 3 * 1280 + 5                                # cell 16, interval 1280: 80 cells per interval, more than a run
+LONG_INTERVAL_CUTS = (1024, 1280, 1281)                            # a run seam inside interval 0, the interval's end, one behind it
+WALK_RUNS = (17, 18, 33, 34)                                       # 16, 17, 32 and 33 steps of level two
+
+
+def run_edge_length(cell):
+    """65 cells and 17 samples: one run seam, one step of level two, a partial last cell."""
+    return 65 * cell + 17
+
+
+TAUS_CASES = [edge("f64x3", T, EDGE_TAUS[n], 32, 480) for n in EDGE_TAUS for T in TAUS_LENGTHS]
+EXTREME_CASES = [edge("f64x2", LONG_INTERVAL_LENGTH if cell == 16 else run_edge_length(cell), (0.002, 0.125), cell, interval)
+                 for cell, interval in ((16, 16), (16, 48), (48, 96), (80, 480), (1024, 1024), (1024, 2048))]
+LONG_INTERVAL_CASE = edge("f64x2", LONG_INTERVAL_LENGTH, (0.002, 0.125), 16, 1280)
+WALK_CASES = [edge("f64x1", (nr - 1) * 1024 + 5, EDGE_TAUS[3], 16, 16 * 64) for nr in WALK_RUNS]
+# a = 1 - 5.2e-6; A = a^1024 and A64 exactly 0; A = 3.3e-15 and A64 = 0
+TABLE_CASES = [edge("f64x2", run_edge_length(1024), (1.0, 0.125), 1024, 1024, fs=192000.0),
+               edge("f64x2", run_edge_length(1024), (20e-6, 0.125), 1024, 1024), edge("f64x2", run_edge_length(32), (20e-6, 0.125), 32, 480)]
+DENORMAL_CASE = edge("unit+noise", run_edge_length(704), (20e-6,), 704, 704)       # A = a^704 = e^-733: a denormal double
+EDGE_CASES = TAUS_CASES + EXTREME_CASES + [LONG_INTERVAL_CASE] + WALK_CASES + TABLE_CASES + [DENORMAL_CASE]
+
+
+def edge_id(case):
+    kind, T, s = case
+    return f"{kind}-{T}-fs{s['fs']:g}-ntau{len(s['taus'])}-tau{min(s['taus']):g}-cell{s['cell']}-int{s['interval']}"
+
+
+# ---- what the GPU test files share -------------------------------------------------------------------------------------------------
+
+def host(v):
+    return v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+
+
+def same_bits(a, b):
+    a, b = host(a), host(b)
+    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+RESULT_FIELDS = "leq lmax lmin level peak_db energy peak count total_leq sel total_lmax total_lmin total_peak_db".split()
+DETECTOR_FIELDS = "energy peak last max min count total_energy total_peak total_max total_min".split()
+
+
+def same_result(a, b, fields=None):
+    for name in fields or (RESULT_FIELDS if hasattr(a, "leq") else DETECTOR_FIELDS):
+        same_bits(getattr(a, name), getattr(b, name))
+
+
+def same_detector_state(a, b):
+    assert (a.rows, a.n, a.final, a.settings) == (b.rows, b.n, b.final, b.settings)
+    same_bits(a.data, b.data)
+
+
+def as_fields(d):
+    return Fields(*(host(getattr(d, n)) for n in ("energy", "peak", "last", "max", "min", "count")))
+
+
+def in_pieces(batch, x, cuts, method="detect", **kw):
+    """The calls over x[..., a:b] for consecutive cuts, the last one flushed: (the results, the last state)."""
+    state, parts = None, []
+    ends = list(cuts) + [x.shape[-1]]
+    for a, b in zip([0] + list(cuts), ends):
+        r = getattr(batch, method)(x[..., a:b], state=state, flush=b == x.shape[-1], **kw)
+        state = r.state
+        parts.append(r)
+    return parts, state
+
+
+def joined(parts, name):
+    axis = 0 if name == "count" else (-2 if name in ("last", "max", "min", "lmax", "lmin", "level") else -1)
+    return np.concatenate([host(getattr(p, name)) for p in parts], axis=axis)
+
+
+def pieces_equal_whole(batch, x, cuts, method="detect", **kw):
+    whole = getattr(batch, method)(x)
+    parts, state = in_pieces(batch, x, cuts, method, **kw)
+    names = ("energy peak last max min count" if method == "detect" else "leq lmax lmin level peak_db energy peak count").split()
+    for name in names:
+        same_bits(joined(parts, name), getattr(whole, name))
+    for name in (DETECTOR_FIELDS[6:] if method == "detect" else RESULT_FIELDS[8:]):
+        same_bits(getattr(parts[-1], name), getattr(whole, name))
+    return whole, state

@@ -16,6 +16,7 @@ import pytest
 import decay_helpers as dh
 import sos_helpers as sh
 import sti_helpers
+from sos_helpers import host, led, parity, run_pieces, same_bits, same_state
 
 pytestmark = pytest.mark.gpu
 
@@ -27,36 +28,6 @@ S = sh.SEAM_CELL
 def mod(hip):
     from friture_amd import sosfilter
     return sosfilter
-
-
-def host(v):
-    return v.cpu().numpy() if hasattr(v, "cpu") else v
-
-
-def same_bits(a, b):
-    a, b = host(a), host(b)
-    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def same_state(a, b):
-    assert a.rows == b.rows and a.n == b.n and a.settings == b.settings
-    same_bits(a.data, b.data)
-
-
-def led(x, lead):
-    """x as a view that starts `lead` elements into a buffer."""
-    buf = np.zeros(lead + x.size, x.dtype)
-    buf[lead:] = x.reshape(-1)
-    return buf[lead:].reshape(x.shape)
-
-
-def parity(y, name, args, label):
-    x, sos, fan, yld, y64 = sh.cached(name, *args)
-    y = host(y).astype(np.float64).reshape(yld.shape)
-    e, d, b = sh.distance(y64, yld), sh.distance(y, yld), sh.bar(y64, yld)
-    print(f"{label}: e_seq {e.max():.2e}, device {d.max():.2e}, largest device / e_seq {(d / np.maximum(e, 1e-300)).max():.1f}, "
-          f"bar {b.min():.2e} .. {b.max():.2e}")
-    assert np.all(d <= b)
 
 
 def float32_bar(y, name, args):
@@ -139,15 +110,6 @@ def test_reverse_is_the_flipped_forward_run(mod, fan):
     same_bits(back.y, forward[..., ::-1])
     t = __import__("torch")
     same_bits(batch.run(t.from_numpy(x).cuda(), fan=fan, reverse=True).y, back.y)
-
-
-def run_pieces(batch, x, cuts, fan):
-    state, parts = None, []
-    for a, b in zip([0] + list(cuts), list(cuts) + [x.shape[-1]]):
-        r = batch.run(x[..., a:b], fan=fan, state=state)
-        state = r.state
-        parts.append(host(r.y))
-    return np.concatenate(parts, axis=-1), state
 
 
 @pytest.mark.parametrize("fan", [True, False])

@@ -93,7 +93,7 @@ def test_default_cell_and_state_length():
 
 
 def cell_form_within_bar(kind, T):
-    w, ref, seq, bar, peak = sl.cached(kind, T)
+    w, ref, seq, bar, peak = sl.cached(kind, T, **sl.SEAM)
     got = sl.cell_form(w, sl.SEAM["fs"], sl.SEAM["taus"], sl.SEAM["cell"], sl.SEAM["interval"])
     for name in ("last", "max", "min"):
         print(f"{kind} {T} {name}: cell form {sl.distance(getattr(got, name), getattr(ref, name), peak).max():.2e}, "

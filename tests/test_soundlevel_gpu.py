@@ -13,6 +13,8 @@ import pytest
 
 import soundlevel_helpers as sl
 from sos_helpers import decaying_noise
+from soundlevel_helpers import (DETECTOR_FIELDS, RESULT_FIELDS, as_fields, host, in_pieces, joined, led, pieces_equal_whole, same_bits,
+                                same_detector_state, same_result)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,74 +33,13 @@ def seam(mod):
     return mod.SoundLevelBatch("Z", **SEAM)
 
 
-def host(v):
-    return v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
-
-
-def same_bits(a, b):
-    a, b = host(a), host(b)
-    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-RESULT_FIELDS = "leq lmax lmin level peak_db energy peak count total_leq sel total_lmax total_lmin total_peak_db".split()
-DETECTOR_FIELDS = "energy peak last max min count total_energy total_peak total_max total_min".split()
-
-
-def same_result(a, b, fields=None):
-    for name in fields or (RESULT_FIELDS if hasattr(a, "leq") else DETECTOR_FIELDS):
-        same_bits(getattr(a, name), getattr(b, name))
-
-
-def same_detector_state(a, b):
-    assert (a.rows, a.n, a.final, a.settings) == (b.rows, b.n, b.final, b.settings)
-    same_bits(a.data, b.data)
-
-
-def as_fields(d):
-    return sl.Fields(*(host(getattr(d, n)) for n in ("energy", "peak", "last", "max", "min", "count")))
-
-
-def led(x, lead):
-    """x as a view that starts `lead` elements into a buffer."""
-    buf = np.zeros(lead + x.size, x.dtype)
-    buf[lead:] = x.reshape(-1)
-    return buf[lead:].reshape(x.shape)
-
-
-def in_pieces(batch, x, cuts, method="detect", **kw):
-    """The calls over x[..., a:b] for consecutive cuts, the last one flushed: (the results, the last state)."""
-    state, parts = None, []
-    ends = list(cuts) + [x.shape[-1]]
-    for a, b in zip([0] + list(cuts), ends):
-        r = getattr(batch, method)(x[..., a:b], state=state, flush=b == x.shape[-1], **kw)
-        state = r.state
-        parts.append(r)
-    return parts, state
-
-
-def joined(parts, name):
-    axis = 0 if name == "count" else (-2 if name in ("last", "max", "min", "lmax", "lmin", "level") else -1)
-    return np.concatenate([host(getattr(p, name)) for p in parts], axis=axis)
-
-
-def pieces_equal_whole(batch, x, cuts, method="detect", **kw):
-    whole = getattr(batch, method)(x)
-    parts, state = in_pieces(batch, x, cuts, method, **kw)
-    names = ("energy peak last max min count" if method == "detect" else "leq lmax lmin level peak_db energy peak count").split()
-    for name in names:
-        same_bits(joined(parts, name), getattr(whole, name))
-    for name in (DETECTOR_FIELDS[6:] if method == "detect" else RESULT_FIELDS[8:]):
-        same_bits(getattr(parts[-1], name), getattr(whole, name))
-    return whole, state
-
-
 # ---- seams --------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("kind", sl.SEAM_KINDS)
 @pytest.mark.parametrize("T", sl.SEAM_LENGTHS)
 def test_parity_on_the_seams(seam, T, kind):
     """interval 480, cell 32, taus 2 ms and 20 ms: 3 float64 rows and 65 float32 rows; the lead-ins 0, 1 and 63 in turn."""
-    w, ref, seq, bar, peak = sl.cached(kind, T)
+    w, ref, seq, bar, peak = sl.cached(kind, T, **SEAM)
     lead = (0, 1, 63)[(sl.SEAM_LENGTHS.index(T) + sl.SEAM_KINDS.index(kind)) % 3]
     d = seam.detect(led(w, lead))
     got = as_fields(d)
@@ -120,7 +61,7 @@ def test_parity_on_the_seams(seam, T, kind):
 @pytest.mark.parametrize("flush", [True, False])
 def test_parity_on_the_long_row(seam, flush):
     """64 * 64 * 32 + 3 samples at cell 32: 65 runs, so level two of the scan walks; two float64 rows."""
-    w, ref, seq, bar, peak = sl.cached("long", sl.LONG_LENGTH)
+    w, ref, seq, bar, peak = sl.cached("long", sl.LONG_LENGTH, **SEAM)
     d = seam.detect(w, flush=flush)
     got = as_fields(d)
     J = sl.LONG_LENGTH // 480 + int(flush)
@@ -155,17 +96,17 @@ def test_default_settings(mod):
 # ---- bit-identity ---------------------------------------------------------------------------------------------------------------
 
 def test_pieces_give_the_bits_of_the_whole(seam):
-    w = sl.cached("f64x3", 2049)[0]
+    w = sl.cached("f64x3", 2049, **SEAM)[0]
     whole, state = pieces_equal_whole(seam, w, (1, 31, 32, 33, 480, 1000))
     same_detector_state(state, whole.state)
     pieces_equal_whole(seam, w[:, :100], range(1, 100))           # one-sample pieces
-    long = sl.cached("long", sl.LONG_LENGTH)[0]                   # and cut inside the second level's runs
+    long = sl.cached("long", sl.LONG_LENGTH, **SEAM)[0]                   # and cut inside the second level's runs
     pieces_equal_whole(seam, long, (64 * 32 * 3 + 5, 2049 * 50, 64 * 32 * 64, 64 * 32 * 64 + 1))
 
 
 def test_what_does_not_matter(seam, mod):
     import torch
-    w = sl.cached("f32x65", 2049)[0]
+    w = sl.cached("f32x65", 2049, **SEAM)[0]
     whole = seam.detect(w)
     per_row = 8 * (2 * (2 * 66 + 2 * 3) + 8 * 66)                 # a little more than one row's scratch: one row per launch
     same_result(seam.detect(w, scratch_bytes=per_row), whole)
@@ -196,7 +137,7 @@ def test_what_does_not_matter(seam, mod):
 
 
 def test_z_run_is_the_detector_in_decibels(seam, mod):
-    w = sl.cached("f64x3", 2049)[0]
+    w = sl.cached("f64x3", 2049, **SEAM)[0]
     d, r = seam.detect(w), seam.run(w)
     with np.errstate(divide="ignore"):
         same_bits(r.leq, 10 * np.log10(d.energy / d.count))
@@ -224,7 +165,7 @@ def test_z_run_is_the_detector_in_decibels(seam, mod):
 # ---- dead data --------------------------------------------------------------------------------------------------------------------
 
 def test_zero_rows_and_a_nan(seam):
-    w = sl.cached("f64x3", 2049)[0]
+    w = sl.cached("f64x3", 2049, **SEAM)[0]
     clean = seam.detect(w)
     bad = w.copy()
     bad[0] = 0.0
