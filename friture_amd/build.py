@@ -44,6 +44,7 @@ EXTRA_FLAGS = {"iir.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-for
                "mtf.hip": ["-ffp-contract=off"],             # X5: the fused multiply-adds of the sums are the ones written out
                "sosfilter.hip": ["-ffp-contract=off"],       # X6: every product of a section and of a scan step rounds on its own
                "soundlevel.hip": ["-ffp-contract=off"],      # X7: a e + g q and P + A s round each product on its own
+               "spatial.hip": ["-ffp-contract=off"],         # X8: the fused multiply-adds of the sums are the ones written out; |l r| rounds its product
                "stft.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"]}
 
 

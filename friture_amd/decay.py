@@ -1,7 +1,8 @@
 """How long a measured room rings: reverberation times and clarity from impulse responses on the GPU (decay.hip, frt_decay_*;
 the definition: X3 in include/friture_hip.h).  The step after impulse_response and ConvolveBatch: Schroeder's backward
 integration and the ISO 3382 numbers of whole batches of responses (responses times bands), from samples to results on the
-device.
+device.  (The two-channel quantities of ISO 3382-1, the inter-aural cross-correlation coefficients and the lateral energy
+fractions of a pair of responses measured at one point: friture_amd/spatial.py, X8.)
 
 A row x[0 .. T) is float32 or float64, 1 <= T <= 2^24; fs defaults to 48000.  All arithmetic is float64: e[t] = (double)x[t]^2.
 Parameters: block W = 480 samples (10 ms at 48 kHz; any integer in 8 .. 65536), onset_db = -20, noise_tail = 0.1, margin_db = 10.

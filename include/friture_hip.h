@@ -1207,6 +1207,67 @@ int frt_spl_run(frt_spl* h, const void* x, int x_dtype, int rows, int64_t n, int
                 const double* state_in, double* state_out, int flush, int64_t scratch_bytes, double* vals, int64_t* count,
                 int64_t* n_intervals);
 
+/* ---- X8: inter-aural cross-correlation and lateral energy from pairs of responses (SpatialBatch) ----------------------------
+ * The reference has no such component; this is the definition (the two-channel quantities of ISO 3382-1: Annex B's IACC of a
+ * binaural pair, and the sums behind Annex A's lateral energy fractions of an omnidirectional / figure-of-eight pair).
+ * A pair is two rows of T samples, 1 <= T <= 2^24, float32 or float64: row 0 is l (the left ear, or the omnidirectional
+ * microphone), row 1 is r (the right ear, or the figure-of-eight).  All arithmetic is float64 on samples converted to double.
+ * Parameters: fs; M = max_lag, an integer in 0 .. 128 (the standard's +-1 ms is round(fs / 1000)); 1 to 4 windows (a_w, b_w) in
+ * samples behind the onset, 0 <= a_w < b_w, b_w = -1 for "to the end"; onset_db = -20.
+ * 1. End: e per pair, 1 <= e <= T (default T).  A sample of either row at an index outside [0, e) counts as zero and is never
+ *    read into a result, whatever it holds.
+ * 2. Dead pair: [0, e) holds a sample that is not finite in either row, or both rows are all zero there (or, in device arrays,
+ *    an end outside 1 .. T or an onset outside 0 .. e - 1).  Every float output is NaN, every index output -1; a dead pair never
+ *    faults and never changes its neighbours' bits.
+ * 3. Peak and onset: P = max over both rows and [0, e) of |x|; peak is the smallest t with max(|l[t]|, |r[t]|) = P; t0 is the
+ *    smallest t with max(|l[t]|, |r[t]|) >= c P, c the double nearest 10^(onset_db / 20), made on the host, the product rounded
+ *    to double: the test is exact.  Or t0 is given per pair, 0 <= t0 < e (the bands of one response share the broadband onset).
+ * 4. Windows: [A_w, B_w) = [min(t0 + a_w, e), min(t0 + b_w, e)), B_w = e for b_w = -1.  An empty window is legal.
+ * 5. Sums over t in [A_w, B_w): El_w = sum l[t]^2, Er_w = sum r[t]^2, X_w = sum |l[t] r[t]|, C_w[tau] = sum l[t] r[t + tau] for
+ *    tau = -M .. M, where r[t + tau] may lie outside the window but not outside [0, e) (the integration runs over t).
+ * 6. IACF_w[tau] = C_w[tau] / sqrt(El_w Er_w); iacc_w = max |IACF_w[tau]|; k_w = the smallest index tau + M in 0 .. 2 M that
+ *    attains it; tau_w = (k_w - M) / fs seconds.  When El_w Er_w = 0 (an empty or a silent window) iacc, tau and IACF are NaN and
+ *    k_w = -1; the sums are still returned.
+ * Order of the sums.  Every sample contributes its 2 M + 1 products once, however the windows overlap: the distinct A_w, B_w of
+ * a pair cut [0, e) into disjoint segments (a segment that no window covers is not summed); a segment is summed in tiles of
+ * frt_spatial_tile() = 2048 samples counted from the segment's start; a window's sum is the sum of its segments in ascending
+ * time, added one by one to 0.  So a window's bits depend on the cut points that other windows put inside it, and with the
+ * windows (0, n80), (n80, end), (0, end) the whole-response window is exactly early + late.  Inside a tile, for M > 0: the tile
+ * is blocks of 8 samples; lane i of 64 takes the blocks i, i + 64, i + 128, i + 192 in that order and inside a block the samples
+ * in order, C[tau] = fma(l[t], r[t + tau], C[tau]), El = fma(l, l, El), Er = fma(r, r, Er), X = X + |l r| with the product
+ * rounded first; the lane sums fold pairwise over the lane distances 32, 16, 8, 4, 2, 1 (C), and by the butterfly xor 32 .. 1
+ * (El, Er, X); both give every lane the same sum.  For M = 0: thread i of 256 takes the samples i, i + 256, .. in order, with the
+ * same four operations, a butterfly folds each wavefront's 64 lanes and the four wavefronts are added in order.  Across the
+ * tiles of a segment: strand i of 16 adds the tiles i, i + 16, .. in order to 0, the strands are added in order.  The
+ * divisions, the square root, the maximum and its index are made on the device.  No atomics.  A pair's bits do not depend on
+ * the other pairs of the call, on scratch_bytes, on any stride, on the input's dtype or on where the buffers live; they do
+ * depend on M (the order of El, Er and X differs between M = 0 and M > 0).
+ * Out of scope: fractional lags, M > 128, a carried state (the onset anchors everything, so a response is given whole), L_J's
+ * 10 m free-field reference (the caller supplies a reference energy), head-related or microphone calibration of any kind. */
+typedef struct frt_spatial frt_spatial;
+/* pure host: the tile length of the correlation */
+int frt_spatial_tile(void);
+/* starts, stops: [windows] HOST integers, samples behind the onset; a stop of -1 is "to the end".  FRT_ERR_INVALID, before any
+ * device call: a null pointer, fs outside 100 .. 1e7, max_lag outside 0 .. 128, windows outside 1 .. 4, a start below 0, a stop
+ * that is neither -1 nor above its start, either above 2^31, onset_db above 0 or not finite. */
+int frt_spatial_create(frt_spatial** h, double fs, int max_lag, const int64_t* starts, const int64_t* stops, int windows,
+                       double onset_db);
+void frt_spatial_destroy(frt_spatial* h);
+/* Launches go to the null stream unless another one is set here. */
+int frt_spatial_set_stream(frt_spatial* h, void* hip_stream);
+/* One call over `pairs` pairs of rows of n samples.  x: float32 (x_dtype 0) or float64 (1); sample t of row c (0: l, 1: r) of
+ * pair s is x[s pair_stride + c row_stride + t] (strides in elements, >= n; the pair stride of a single pair is not read).
+ * onset: [pairs] or NULL (step 3 finds it); stop: [pairs] ends e or NULL (e = n).  With W windows: params [pairs][W][5] = iacc,
+ * tau, X, El, Er; indices [pairs][W + 2] = k_0 .. k_(W-1), peak, onset; iacf [pairs][W][2 max_lag + 1] or NULL.  The pairs are
+ * cut into slabs whose scratch stays within scratch_bytes (at least one pair per launch); the result does not depend on it.
+ * Host or device buffers in any mix (host ones are staged); one synchronisation at the end.  FRT_ERR_INVALID, before any
+ * launch: a null handle, an unknown x_dtype, pairs outside 1 .. 65535, n outside 1 .. 2^24, a null x, a bad stride,
+ * scratch_bytes < 0, null params or indices, and in host arrays a stop outside 1 .. n, an onset outside 0 .. n - 1 or an onset
+ * at or behind its pair's stop. */
+int frt_spatial_run(frt_spatial* h, const void* x, int x_dtype, int pairs, int64_t n, int64_t row_stride, int64_t pair_stride,
+                    const int64_t* onset, const int64_t* stop, int64_t scratch_bytes, double* params, int64_t* indices,
+                    double* iacf);
+
 #ifdef __cplusplus
 }
 #endif
