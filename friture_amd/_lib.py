@@ -232,6 +232,12 @@ SIGNATURES = {
     "frt_spatial_set_stream": (c_int, [c_void_p, c_void_p]),
     "frt_spatial_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                 c_void_p, c_void_p]),
+    "frt_tone_create": (c_int, [POINTER(c_void_p), c_int, c_int64, POINTER(c_double), c_int, c_int, c_int, c_int, POINTER(c_int),
+                                POINTER(c_int), c_int, c_double]),
+    "frt_tone_destroy": (None, [c_void_p]),
+    "frt_tone_set_stream": (c_int, [c_void_p, c_void_p]),
+    "frt_tone_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                             POINTER(c_int64)]),
     "frt_lfilter_f64":(c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), c_int, POINTER(c_double),
                                 POINTER(c_double), POINTER(c_double)]),
 }

@@ -45,6 +45,7 @@ EXTRA_FLAGS = {"iir.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-for
                "sosfilter.hip": ["-ffp-contract=off"],       # X6: every product of a section and of a scan step rounds on its own
                "soundlevel.hip": ["-ffp-contract=off"],      # X7: a e + g q and P + A s round each product on its own
                "spatial.hip": ["-ffp-contract=off"],         # X8: the fused multiply-adds of the sums are the ones written out; |l r| rounds its product
+               "distortion.hip": ["-ffp-contract=off"],      # X9: k Q[k] rounds before it is added; every product of the transform rounds on its own
                "stft.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"]}
 
 

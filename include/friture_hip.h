@@ -1268,6 +1268,64 @@ int frt_spatial_run(frt_spatial* h, const void* x, int x_dtype, int pairs, int64
                     const int64_t* onset, const int64_t* stop, int64_t scratch_bytes, double* params, int64_t* indices,
                     double* iacf);
 
+/* ---- X9: total harmonic distortion, noise and harmonic levels of tone recordings (ToneBatch) ----------------------------
+ * The reference has no such component; this is the definition.  A stream is one row of samples of a system driven by a sine;
+ * float64 arithmetic whatever the input dtype (a float32 sample widens exactly).
+ * Settings: fft_size N, a power of two in 512 .. 16384; hop, 1 .. 2^30, which may exceed N; a window w of N doubles; the
+ * half-width of a spectral line L = lobe, 1 .. 16 bins; the highest order H = harmonics, 2 .. 32; the band ka .. kb in bins,
+ * L + 1 <= ka <= kb <= N/2; one search range klo .. khi for all streams or one per stream, ka + L <= klo <= khi <= kb - L; a
+ * gate g >= 0, a power.  (ToneBatch derives them from Hz and dB on the host: ka = max(L + 1, ceil(f_lo N / fs)), kb =
+ * min(N/2, floor(f_hi N / fs)), klo = ka + L and khi = kb - L intersected with rint(f0 N / fs) +- L when f0 is given, g the
+ * double nearest 10^(gate_db / 10); an empty range is an error there.)
+ * Frames: frame f of a stream is its samples [f hop, f hop + N); only complete frames count: F(n) = 0 for n < N, else
+ * floor((n - N) / hop) + 1.
+ * Spectrum: X = rfft(x w); Q[k] = c_k |X[k]|^2 / (N sum_n w[n]^2), c_k = 2 except c_0 = c_(N/2) = 1: a unit sine's line sums
+ * to 0.5.  (The device multiplies |X[k]|^2 by the double nearest c_k / (N sum w^2), the sum made in index order on the host.)
+ * Fundamental: c1 = the arg-max of Q over klo .. khi, the lowest index on ties; P1 = sum of Q[c1 - L .. c1 + L], ascending k
+ * from 0; kappa = (sum k Q[k]) / P1 over the same bins, each product rounded and added in the same order.
+ * Harmonics h = 2 .. H: c_h = rint((double)h * kappa), half to even, and c_1 = c1.  Order h is present when c_h + L <= kb; its
+ * lobe is [max(c_h - L, c_(h-1) + L + 1), c_h + L], so a bin counts once, for the lowest order that holds it; P_h is the sum
+ * over the lobe, ascending k from 0.  An absent order has no lobe: it is NaN in the output and adds 0 to the totals.
+ * Residual: R = the sum of Q[k] over ka <= k <= kb outside every lobe of the orders 1 .. H.  No power is obtained by
+ * subtraction.  Its order: thread i of N/16 sums the bins i, i + N/16, .. , i + 7 N/16 in that order from 0 (thread 0 then
+ * adds bin N/2), a bin outside the band or inside a lobe counting as +0; the thread sums of each 64 consecutive threads (32
+ * for N = 512) fold as a balanced binary tree over neighbours ((t0 + t1) + (t2 + t3) ..); the groups of 64 are added in order.
+ * Dead frame: it holds a sample that is not finite, or Q is all zero over klo .. khi.  kappa, P1, R and every P_h are NaN,
+ * peak_bin = -1, not valid.  Gated frame: a live frame with P1 < g; it keeps its values and is not valid.
+ * A frame of finite samples whose Q overflows (samples near 1e154 and above) is live: its values are inf or NaN as the sums give
+ * them, it is valid unless gated, and the totals of its stream become inf or NaN with it; no order of such a frame is present.
+ * Totals per stream: n_valid and the left folds from 0, in frame order over the valid frames, of kappa, P1, R and each P_h.
+ * They do not depend on how a recording is cut into calls, slabs or batches.  No atomics.
+ * The state after n samples is one array of doubles, S the number of streams,
+ *   totals [S][3 + H] (sum kappa, sum P1, sum R, sum P_2 .. sum P_H, n_valid) | the row from min(n, F(n) hop) on [S][..]
+ * (at most N - 1 samples per row), and the results of a call that completes F frames are another,
+ *   kappa [S][F] | P1 [S][F] | R [S][F] | P_h [S][F][H - 1] | code [S][F], code = -1 for a dead frame, else 2 c1 + valid.
+ * Out of scope: frames above 16384, weighting curves on Q, spurs, two-tone intermodulation, harmonic phases, notch-filter
+ * time-domain THD+N, multi-tone signals. */
+typedef struct frt_tone frt_tone;
+/* window: [fft_size] HOST doubles; klo, khi: [n_search] HOST integers, n_search = 1 or the number of streams of every run.
+ * FRT_ERR_INVALID, before any device call: fft_size outside 512 .. 16384 or no power of two, hop outside 1 .. 2^30, lobe
+ * outside 1 .. 16, harmonics outside 2 .. 32, a band outside lobe + 1 .. fft_size / 2 or empty, n_search outside 1 .. 65535, a
+ * search range that is empty or outside ka + lobe .. kb - lobe, a gate that is negative or not finite, a null, non-finite or
+ * all-zero window. */
+int frt_tone_create(frt_tone** h, int fft_size, int64_t hop, const double* window, int lobe, int harmonics, int ka, int kb,
+                    const int* klo, const int* khi, int n_search, double gate);
+void frt_tone_destroy(frt_tone* h);
+/* Launches go to the null stream unless another one is set here. */
+int frt_tone_set_stream(frt_tone* h, void* hip_stream);
+/* One call over `streams` rows.  x: float32 (x_dtype 0) or float64 (1); sample t of stream s is x[s row_stride + t] (stride in
+ * elements, >= n; a single stream's is not read), the samples first_in .. first_in + n - 1 of the streams (n = 0: x may be
+ * NULL).  state_in: the state after first_in samples (NULL: new streams, first_in = 0 only); state_out: the state after the
+ * call, a buffer distinct from state_in; out: the results (may be NULL when no frame completes); n_frames_out (may be NULL): F.
+ * The frame records of one launch, 3 + H doubles per frame and stream, stay within scratch_bytes (at least one frame per
+ * launch): the frames are cut into time slabs, and the result does not depend on it.  Host or device buffers in any mix (host
+ * ones are staged); one synchronisation at the end.  FRT_ERR_INVALID, before any device call: a null handle, an unknown
+ * x_dtype, streams outside 1 .. 65535 or not the handle's n_search when that is above 1, n < 0, a bad stride, first_in < 0 or
+ * first_in + n > 2^40, first_in > 0 without state_in, a null state_out or one equal to state_in, scratch_bytes < 0, a null out
+ * when frames complete. */
+int frt_tone_run(frt_tone* h, const void* x, int x_dtype, int streams, int64_t n, int64_t row_stride, const double* state_in,
+                 double* state_out, int64_t first_in, int64_t scratch_bytes, double* out, int64_t* n_frames_out);
+
 #ifdef __cplusplus
 }
 #endif
